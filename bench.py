@@ -12,7 +12,9 @@ parallelism, one RCCL all-reduce of the flat gradient bucket per step.
 itself (a `torch.distributed.run` child process, before anything touches the GPU),
 relays rank 0's JSON line and exits with the child's code.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement), with
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, `config`) and `roofline_mfma` (arithmetic on the step time).  A plain
+run does nothing else: set up, warm up, time the steps, print.  `--full` adds
   roofline        — the lattice forward-backward scan kernel of the step, HBM-bound,
                     timed live with events on the stream it is launched on;
   roofline_bichar — the scan on the bi-char numerator (C = 2401, B = 512), launched alone
@@ -22,7 +24,6 @@ Prints ONE JSON line on rank 0 (see the contract in the task statement), with
                     bi-char CTC (ctc_bi) and bi-char CTC-G + CDE (ctcg_bi_cde), a few timed
                     steps each after the headline region (with N > 1: the bi-char step, the
                     model of config 5, on all ranks);
-  roofline_mfma   — dense flops of the step / step time / 2.5 PFLOP/s (bf16 dense peak);
   decode          — BASELINE config 4 beside the headline: utterances/s of the TCN attention
                     decoder with beam 10 (N = 1 only);
   loss_delta      — |loss_gpu - loss_cpu| / |loss_cpu| of one small batch, product
@@ -30,6 +31,12 @@ Prints ONE JSON line on rank 0 (see the contract in the task statement), with
                     (end to end, and decoder + lattice on identical encoder output);
   cpu_baseline    — the same step on the host cores (torch-CPU encoder + the CPU
                     oracle for the lattice), bounded sample, N = 1 only.
+roofline_mfma is dense flops of the step / step time / 2.5 PFLOP/s (bf16 dense peak).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller, on rank 0, as
+DIR/<name>.npy (see dump_step_outputs): the loss dict, the model state after the update and
+the parameter gradients.  Inputs and initial weights are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -455,6 +462,52 @@ def pmc_traffic(order, B, T, kernel_tag=None, grid=None):
         return None
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6        # data bytes of one --dump-outputs directory (64 MB cap, headers aside)
+DUMP_WHOLE_ELEMS = 1024                 # arrays up to this size are always written whole
+
+
+def dump_step_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write `arrays` (name -> numpy array) as out_dir/<name>.npy, float64 arrays as float64 and
+    everything else as float32.  When the whole set is larger than `budget`, every array above
+    DUMP_WHOLE_ELEMS elements is replaced by the same fraction of its flattened elements, at
+    indices drawn from a generator seeded by the array's name (the same sample in every run).
+    Returns {name: 'whole' | 'sampled'}."""
+    import zlib
+    conv = {n: np.asarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+            for n, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    frac = min(1.0, budget / float(total)) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    kinds = {}
+    for n, a in conv.items():
+        keep = max(DUMP_WHOLE_ELEMS, int(a.size * frac))
+        if keep < a.size:
+            idx = np.random.default_rng(zlib.crc32(n.encode())).choice(a.size, keep, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+            kinds[n] = 'sampled'
+        else:
+            kinds[n] = 'whole'
+        np.save(os.path.join(out_dir, n + '.npy'), a)
+    return kinds
+
+
+def step_output_arrays(out, model, params):
+    """What one training step hands its caller: the loss dict it returned (`out.<key>`), the model
+    state after the update (`state.<name>`, parameters and buffers) and the gradients the update
+    used (`grad.<name>`, the bucket's views)."""
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays['out.' + k] = v.detach().cpu().numpy()
+    for k, v in model.state_dict().items():
+        arrays['state.' + k] = v.detach().cpu().numpy()
+    names = {id(p): n for n, p in model.named_parameters()}
+    for p in params:
+        if p.grad is not None:
+            arrays['grad.' + names[id(p)]] = p.grad.detach().cpu().numpy()
+    return arrays
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -471,7 +524,14 @@ def main():
                          "channels, the shape of the WSJ recipes' real features (egs/wsj/yamls/ctc.yaml:8-15)")
     ap.add_argument('--workload', default=None, choices=sorted(WORKLOADS),
                     help='BASELINE config; default ctc (mono-char, the headline metric)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what lies beside the headline: lattice roofline of the '
+                         'timed steps, bi-char roofline launch, extra workloads, decode rate, loss delta '
+                         'and CPU baseline (a plain run only times the steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (loss dict, model state after the update, "
+                         'gradients) as DIR/<name>.npy, at most 64 MB (a fixed sample of larger sets)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave out the CPU baseline and loss delta')
     ap.add_argument('--no-hooks', action='store_true',
                     help='leave out GradientClipping / PolyakDecay (recipe hooks)')
     ap.add_argument('--host-step', action='store_true',
@@ -481,9 +541,12 @@ def main():
                     help='N > 1: BatchNorm statistics over all replicas (att_speech.dp.enable_sync_batchnorm), '
                          'as in the single-process reference, instead of per replica')
     ap.add_argument('--no-extra', action='store_true',
-                    help='leave out the bi-char numerator roofline launch and the decode rate')
+                    help='--full: leave out the extra workloads, the bi-char numerator roofline launch '
+                         'and the decode rate')
     ap.add_argument('--dry-run-launcher', action='store_true', help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         self_launch(a, sys.argv[1:])             # does not return
@@ -528,11 +591,12 @@ def main():
     # The training lattices are built ON the device every step from the labels
     # (asr_ctc_graph_build; the reference builds them per batch with OpenFst in
     # its data workers, kaldi_dataset.py:230-232, and copies 8 padded tensors).
-    # The host builder is used once, outside the timed region, to count arcs
-    # for the algorithmic-bytes formula.
-    n_arcs = (model.decoder.graph_generator.get_training_matrices_batch(texts, llens)[2]
-              > -1e19).sum((1, 2)).numpy()
-    enc_lens = ((lens + 2) // 3).numpy()
+    # With --full the host builder is used once, outside the timed region, to count
+    # arcs for the algorithmic-bytes formula.
+    if a.full:
+        n_arcs = (model.decoder.graph_generator.get_training_matrices_batch(texts, llens)[2]
+                  > -1e19).sum((1, 2)).numpy()
+        enc_lens = ((lens + 2) // 3).numpy()
 
     lat_events = []
     _native.EVENT_HOOK = None
@@ -572,13 +636,13 @@ def main():
     skipped = []
 
     def step(record=False):
-        fwd.on = record
+        fwd.on = record and a.full                       # lattice launch events for `roofline`
         with contextlib.redirect_stdout(sys.stderr):     # hooks print like the reference; stdout is the JSON line
             out, skip = train_step(model, opt, ((feats_d, lens, None, texts, llens), {}),
                                    hooks=hooks, bucket=bucket, forward=fwd, fused=fused)
         if record:
             skipped.append(bool(skip))
-        return out['loss']
+        return out
 
     def fence():
         torch.cuda.synchronize()
@@ -594,7 +658,7 @@ def main():
 
     loss0 = None
     for i in range(a.warmup):
-        l = step()
+        l = step()['loss']
         torch.cuda.synchronize()
         if loss0 is None:
             loss0 = float(l.detach())
@@ -602,8 +666,9 @@ def main():
     fence()
     t0 = time.time()
     for _ in range(a.steps):
-        loss = step(record=True)
+        out = step(record=True)
     fence()
+    loss = out['loss']
     dt = time.time() - t0
     if fused is not None:        # the device's decisions of the timed steps, read after the fence
         skipped = [s_ or rec[2] for s_, rec in zip(skipped, fused.drain()[-a.steps:])]
@@ -622,11 +687,16 @@ def main():
     lstm_err = getattr(_native, 'lstm_check_errors', None)
     if lstm_err is not None:
         lstm_err()                               # raises if a persistent-LSTM hand-off timed out
+    if a.dump_outputs and rank == 0:
+        kinds = dump_step_outputs(a.dump_outputs, step_output_arrays(out, model, bucket.params))
+        progress('outputs of the last timed step: %d arrays (%d sampled) in %s'
+                 % (len(kinds), sum(k == 'sampled' for k in kinds.values()), a.dump_outputs))
+    del out
 
     # BASELINE configs 3 and 5 beside the headline (every rank takes part when N > 1)
     extra = []
-    if not a.no_extra and a.workload in (None, 'ctc') and order == 1:
-        final_state = model.state_dict() if rank == 0 else None
+    final_state = model.state_dict() if rank == 0 else None
+    if a.full and not a.no_extra and a.workload in (None, 'ctc') and order == 1:
         del feats_d, bucket, opt
         torch.cuda.empty_cache()
         # (the batch of the headline: the persistent LSTM grid is sized for 768 utterances per GPU,
@@ -636,14 +706,8 @@ def main():
             progress('extra workload %s' % wl)
             extra.append(time_extra_workload(wl, wb, T, 5, 2, dev, rank, world, not a.no_hooks,
                                              not a.host_step))
-    else:
-        final_state = model.state_dict() if rank == 0 else None
 
     if rank == 0:
-        lat_ms = [s.elapsed_time(e) for (s, e) in lat_events]
-        lat_ms = float(np.mean(lat_ms)) if lat_ms else float('nan')
-        alg = lattice_algorithmic_bytes(enc_lens, C, llens.numpy(), n_arcs)
-        achieved = alg / (lat_ms * 1e-3) / 1e9
         flops = step_flops(B, T, C)
         tflops = flops * world * a.steps / dt / 1e12
         hook_txt = '' if a.no_hooks else ('GradientClipping(clip %g, skip %g = recipe x global_batch/16)'
@@ -669,31 +733,33 @@ def main():
                        'step_boundary': ('device: att_speech.fused_step (clip / skip decision + Adam, no read-back)'
                                          if fused is not None else 'host: hook + torch.optim.Adam, one read-back'),
                        'first_loss': loss0, 'final_loss': float(loss.detach())},
-            'roofline': {'bound': 'hbm', 'kernel': 'lattice_fwbw (alpha/beta scan): %s' % (
-                             mono_lattice_kernel(B) if order == 1 else 'lattice_fwbw_sl_kernel<3, 8, 0>'),
-                         'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBPS, 'traffic': pmc_traffic(order, B, T),
-                         'algorithmic_bytes_per_launch': alg,
-                         'avg_launch_ms': lat_ms},
             'roofline_mfma': {'bound': 'mfma', 'kernel': 'whole step (conv + BiLSTM + projection, fwd+bwd)',
                               'achieved': tflops, 'peak': MFMA_PEAK_TFLOPS * world, 'unit': 'TFLOP/s',
                               'frac': tflops / (MFMA_PEAK_TFLOPS * world),
                               'flops_per_step_per_gpu': flops},
+            'extra_workloads': extra, 'cpu_baseline': None, 'loss_delta': None,
         }
-        if world == 1 and not a.no_extra:
+        if a.full:
+            lat_ms = [s.elapsed_time(e) for (s, e) in lat_events]
+            lat_ms = float(np.mean(lat_ms)) if lat_ms else float('nan')
+            alg = lattice_algorithmic_bytes(enc_lens, C, llens.numpy(), n_arcs)
+            achieved = alg / (lat_ms * 1e-3) / 1e9
+            res['roofline'] = {'bound': 'hbm', 'kernel': 'lattice_fwbw (alpha/beta scan): %s' % (
+                                   mono_lattice_kernel(B) if order == 1 else 'lattice_fwbw_sl_kernel<3, 8, 0>'),
+                               'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                               'frac': achieved / HBM_PEAK_GBPS, 'traffic': pmc_traffic(order, B, T),
+                               'algorithmic_bytes_per_launch': alg,
+                               'avg_launch_ms': lat_ms}
+        if a.full and world == 1 and not a.no_extra:
             progress('bi-char numerator roofline launch')
             res['roofline_bichar'] = bichar_numerator_roofline(
                 dev, traffic=pmc_traffic(2, B, T, 'lattice_fwbw_sl_kernel<3, 8, 0>', grid=512 * 512))
             torch.cuda.empty_cache()
             progress('stage-2 decode rate')
             res['decode'] = tcn_decode_rate(dev)
-        res['extra_workloads'] = extra
-        if world == 1 and not a.no_cpu_baseline and a.workload != 'ctcg_bi_cde':
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload != 'ctcg_bi_cde':
             progress('loss delta + timing the CPU baseline (about 25 s)')
             res['cpu_baseline'], res['loss_delta'] = cpu_baseline(T, order, dev, final_state)
-        else:
-            res['cpu_baseline'] = None
-            res['loss_delta'] = None
         print(json.dumps(res), file=_STDOUT, flush=True)
     if world > 1:
         dist.destroy_process_group()

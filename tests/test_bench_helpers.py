@@ -118,3 +118,55 @@ def test_gpus_n_without_rank_environment_launches_the_ranks():
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env2, timeout=120,
                        universal_newlines=True)
     assert r.returncode != 0 and r.stdout.strip() == ''
+
+
+def test_dump_step_outputs_whole_then_sampled(tmp_path):
+    """--dump-outputs: float32 / float64 files, whole arrays under the budget, above it the same
+    seeded sample of every large array in every run, and the data within the budget."""
+    b = load(os.path.join(ROOT, 'bench.py'), 'bench_mod5')
+    rng = np.random.default_rng(0)
+    arrays = {'out.loss': np.array(3.5, np.float32), 'state.w': rng.standard_normal((300, 40)),
+              'state.n': np.array(7, np.int64), 'grad.w': rng.standard_normal((300, 40)).astype(np.float32)}
+    kinds = b.dump_step_outputs(str(tmp_path / 'a'), arrays)
+    assert set(kinds.values()) == {'whole'}
+    for n, want in arrays.items():
+        got = np.load(str(tmp_path / 'a' / (n + '.npy')))
+        assert got.dtype == (np.float64 if want.dtype == np.float64 else np.float32)
+        assert got.shape == want.shape and np.array_equal(got, want.astype(got.dtype))
+    budget = 40000
+    k1 = b.dump_step_outputs(str(tmp_path / 'b'), arrays, budget=budget)
+    k2 = b.dump_step_outputs(str(tmp_path / 'c'), arrays, budget=budget)
+    assert k1 == k2 == {'out.loss': 'whole', 'state.w': 'sampled', 'state.n': 'whole', 'grad.w': 'sampled'}
+    total = 0
+    for n, want in arrays.items():
+        got, again = (np.load(str(tmp_path / d / (n + '.npy'))) for d in ('b', 'c'))
+        assert np.array_equal(got, again)
+        if k1[n] == 'sampled':
+            assert got.ndim == 1 and b.DUMP_WHOLE_ELEMS <= got.size < want.size
+            assert np.isin(got, want.astype(got.dtype)).all()
+        total += got.nbytes
+    assert total <= budget + len(arrays) * b.DUMP_WHOLE_ELEMS * 8
+
+
+def test_step_output_arrays_names_what_the_caller_receives():
+    import torch
+    b = load(os.path.join(ROOT, 'bench.py'), 'bench_mod6')
+    model = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.BatchNorm1d(2))
+    loss = model(torch.ones(4, 3)).square().sum()
+    loss.backward()
+    arrays = b.step_output_arrays({'loss': loss, 'note': 'not an array'}, model, list(model.parameters()))
+    assert float(arrays['out.loss']) == float(loss)
+    assert set(k for k in arrays if k.startswith('state.')) == set('state.' + k for k in model.state_dict())
+    assert set(k for k in arrays if k.startswith('grad.')) == set('grad.' + n for n, _ in model.named_parameters())
+    assert np.array_equal(arrays['grad.0.weight'], model[0].weight.grad.numpy())
+
+
+def test_bench_options_for_full_and_dump_outputs():
+    """The plain run times the steps; --full carries what lies beside the headline."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120, universal_newlines=True)
+    assert r.returncode == 0 and '--full' in r.stderr and '--dump-outputs' in r.stderr     # stdout: the JSON line only
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0', '--dry-run-launcher'],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120, universal_newlines=True)
+    assert r.returncode != 0 and r.stdout.strip() == ''

@@ -32,7 +32,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('fetch_dir'); ap.add_argument('write_dir'); ap.add_argument('out')
     ap.add_argument('--batch', type=int, required=True)
-    ap.add_argument('--cmd', default='bench.py --steps 2 --warmup 1 --no-cpu-baseline')
+    ap.add_argument('--cmd', default='bench.py --full --steps 2 --warmup 1 --no-cpu-baseline')
     a = ap.parse_args()
     fe, wr = collect(a.fetch_dir, 'FETCH_SIZE'), collect(a.write_dir, 'WRITE_SIZE')
     kernels = {}
