@@ -38,7 +38,8 @@ enum {
     ASR_ELAUNCH = 3      /* HIP reported a launch error */
 };
 
-/* Library / ABI version, bumped when a signature changes. */
+/* Library / ABI version, bumped when a signature changes (23: the noise and non-finite-flag
+ * entry points, asr_adam_clip_step_ex_f32). */
 int asr_abi_version(void);
 
 /* Human-readable text for an ASR_* code (static storage). */
@@ -588,6 +589,63 @@ int asr_adam_clip_step_f32(const AsrAdamChunk *chunks, int nchunks, const float 
                            const uint32_t *err_word, float lr, float beta1, float beta2, float eps,
                            float weight_decay, float clip_norm, float skip_norm,
                            const int32_t *step_in, int32_t *step_out, float *stats, void *stream);
+
+/*
+ * asr_adam_clip_step_f32 with one more skip request (ABI v23): the reference's KillOnNan hook
+ * (att_speech/modules/hooks/kill_on_nan.py:14-27, a `loss.item()` per step that asks the trainer,
+ * trainer.py:241-248, to skip the optimizer step when the loss is NaN or +-inf) decided on the
+ * device.  skip_word (may be NULL) != 0 skips the step, OR-ed with the norm / non-finite norm /
+ * err_word rules; stats [5] = {norm, clipped, skipped, err, skip_word != 0} when skip_word is
+ * given (stats [4] as before when it is NULL).  asr_adam_clip_step_f32 is this entry with
+ * skip_word = NULL, bit for bit.
+ */
+int asr_adam_clip_step_ex_f32(const AsrAdamChunk *chunks, int nchunks, const float *g_flat,
+                              float *m_flat, float *v_flat, const float *partials, int nparts,
+                              const uint32_t *err_word, float lr, float beta1, float beta2, float eps,
+                              float weight_decay, float clip_norm, float skip_norm,
+                              const int32_t *step_in, int32_t *step_out, const uint32_t *skip_word,
+                              float *stats, void *stream);
+
+/*
+ * The loss test of KillOnNan (kill_on_nan.py:16-22: `torch.isnan(loss).item()`, `loss.item() ==
+ * INF or loss.item() == MINF`) without the read-back (ABI v23): *flag = 1 when any of x [n] is
+ * NaN or +-inf, 0 otherwise; one single-workgroup launch, meant for the loss (n small).  The flag
+ * feeds asr_adam_clip_step_ex_f32's skip_word.
+ */
+int asr_nonfinite_flag_f32(const float *x, int n, uint32_t *flag, void *stream);
+
+/*
+ * Counter-based Gaussian noise (ABI v23): the reference's weight noise
+ * (att_speech/modules/hooks/weight_noise.py:63-99: `randn_like(weight) * sigma` added before the
+ * forward pass, the stored tensor subtracted after backward) and ConstantGradientNoise
+ * (gradient_noise.py:10-16: `grad += randn_like(grad) * sigma`) as one launch over a table of
+ * pieces, with nothing stored between the two passes.
+ *
+ * segs (device memory, nsegs entries): `data` = address of a piece of fp32 memory, `index` = the
+ * global noise index of its first element (index + count < 2^34), `count` <= asr_noise_chunk_elems(),
+ * `sigma`.  z[i] for global index i is Philox4x32-10 with key = (seed lo, seed hi) and counter =
+ * (i >> 2, tag, iteration lo, iteration hi); its four output words x0..x3 give
+ * z[4g], z[4g+1] from (x0, x1) and z[4g+2], z[4g+3] from (x2, x3) by Box-Muller:
+ * u = (x >> 9) * 2^-23 + 2^-24, r = sqrtf(-2 logf(u_a)), (s, c) = sincospif(2 u_b),
+ * z_a = r c, z_b = r s.  z depends on (seed, tag, iteration, i) only: not on addresses, the
+ * launch shape or the process.
+ *   mode ASR_NOISE_APPLY: data[k] = data[k] + sign * (sigma * z) with sign = +1 or -1, product and
+ *                         sum each rounded once (no FMA): apply(+1) then apply(-1) is
+ *                         `w.add_(rand); w.add_(-rand)` with rand = sigma * z in fp32;
+ *   mode ASR_NOISE_WRITE: data[k] = z (sigma and sign unused).
+ * tag 0 is weight noise, tag 1 gradient noise.
+ */
+typedef struct AsrNoiseSegment {
+    void *data;
+    uint64_t index;
+    uint32_t count;
+    float sigma;
+} AsrNoiseSegment;
+#define ASR_NOISE_APPLY 0
+#define ASR_NOISE_WRITE 1
+int asr_noise_chunk_elems(void);
+int asr_gaussian_noise_f32(const AsrNoiseSegment *segs, int nsegs, uint64_t seed, uint32_t tag,
+                           uint64_t iteration, int mode, int sign, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,11 @@ Same arithmetic as the hook + torch.optim.Adam (amsgrad / maximize off, weight_d
 tests/test_fused_step_gpu.py compares parameters, moments and decisions with them over several
 steps, including clipped, skipped, non-finite and LSTM-error steps.  `export_state()` writes the
 moments into a torch.optim.Adam's state so that the reference's checkpointer saves what it
-always saved."""
+always saved.
+
+`kill_on_nan` (a KillOnNan hook): the hook's device flag — loss not finite, MAX-reduced over the
+ranks — skips the step too (asr_adam_clip_step_ex_f32), and `poll()` hands the hook each step's
+flag so that it counts and ends the run as the reference does, a few steps late."""
 import ctypes
 
 import numpy as np
@@ -28,7 +32,8 @@ class FusedClipAdam(object):
     RING = 64          # steps whose statistics may be in flight
 
     def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 clip_norm=float('inf'), skip_step_norm=float('inf'), clipping_hook=None):
+                 clip_norm=float('inf'), skip_step_norm=float('inf'), clipping_hook=None,
+                 kill_on_nan=None):
         self.bucket = bucket
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.clip_norm, self.skip_step_norm = float(clip_norm), float(skip_step_norm)
@@ -43,25 +48,31 @@ class FusedClipAdam(object):
         self.partials = torch.empty(self.nparts, dtype=torch.float32, device=dev)
         self.step_words = torch.zeros(2, dtype=torch.int32, device=dev)
         self.calls = 0
-        self.stats_dev = torch.zeros(self.RING, 4, dtype=torch.float32, device=dev)
-        self.stats_host = torch.zeros(self.RING, 4, dtype=torch.float32).pin_memory()
+        # a KillOnNan hook in device mode: its flag word also skips the step (the _ex entry point),
+        # and the 5th stats column it leaves tells poll() what to count
+        self.kill_on_nan = kill_on_nan
+        self._skip_word = None if kill_on_nan is None else kill_on_nan.attach_device(dev)
+        ncols = 4 if kill_on_nan is None else 5
+        self.stats_dev = torch.zeros(self.RING, ncols, dtype=torch.float32, device=dev)
+        self.stats_host = torch.zeros(self.RING, ncols, dtype=torch.float32).pin_memory()
         self.pending = []          # (call index, event)
         self.history = []          # (norm, clipped, skipped, err) of completed steps, in order
         self._ptrs = None
         self._chunks = None
 
     @classmethod
-    def from_optimizer(cls, optimizer, bucket, clipping_hook=None):
+    def from_optimizer(cls, optimizer, bucket, clipping_hook=None, kill_on_nan=None):
         """Hyper-parameters of a torch.optim.Adam (one parameter group) and the thresholds of a
-        GradientClipping hook, whose statistics keep being fed (a few steps late)."""
+        GradientClipping hook, whose statistics keep being fed (a few steps late); `kill_on_nan`
+        (a KillOnNan hook) is switched to device mode and counts what the device decided."""
         if len(optimizer.param_groups) != 1:
             raise NotImplementedError('one parameter group')
         g = optimizer.param_groups[0]
         if g.get('amsgrad') or g.get('maximize'):
             raise NotImplementedError('amsgrad / maximize')
-        kw = {}
+        kw = dict(kill_on_nan=kill_on_nan)
         if clipping_hook is not None:
-            kw = dict(clip_norm=clipping_hook.clip_norm, skip_step_norm=clipping_hook.skip_step_norm,
+            kw.update(clip_norm=clipping_hook.clip_norm, skip_step_norm=clipping_hook.skip_step_norm,
                       clipping_hook=clipping_hook)
         return cls(bucket, lr=g['lr'], betas=g['betas'], eps=g['eps'], weight_decay=g['weight_decay'], **kw)
 
@@ -103,11 +114,15 @@ class FusedClipAdam(object):
         _native.check(L.asr_grad_sumsq_partials_f32(p(flat), flat.numel(), p(self.partials), self.nparts, st),
                       'asr_grad_sumsq_partials_f32')
         sin, sout = self.step_words[k & 1:], self.step_words[(k + 1) & 1:]
-        _native.check(L.asr_adam_clip_step_f32(
-            p(chunks), self._nchunks, p(flat), p(self.m), p(self.v), p(self.partials), self.nparts,
-            p(err_word) if err_word is not None else None, self.lr, self.betas[0], self.betas[1], self.eps,
-            self.weight_decay, self.clip_norm, self.skip_step_norm, p(sin), p(sout),
-            p(self.stats_dev[slot]), st), 'asr_adam_clip_step_f32')
+        args = (p(chunks), self._nchunks, p(flat), p(self.m), p(self.v), p(self.partials), self.nparts,
+                p(err_word) if err_word is not None else None, self.lr, self.betas[0], self.betas[1],
+                self.eps, self.weight_decay, self.clip_norm, self.skip_step_norm, p(sin), p(sout))
+        if self._skip_word is None:
+            _native.check(L.asr_adam_clip_step_f32(*args, p(self.stats_dev[slot]), st),
+                          'asr_adam_clip_step_f32')
+        else:
+            _native.check(L.asr_adam_clip_step_ex_f32(*args, p(self._skip_word), p(self.stats_dev[slot]), st),
+                          'asr_adam_clip_step_ex_f32')
         self.stats_host[slot].copy_(self.stats_dev[slot], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -120,7 +135,8 @@ class FusedClipAdam(object):
         done = []
         while self.pending and self.pending[0][1].query():
             k, _ = self.pending.pop(0)
-            norm, clipped, skipped, err = self.stats_host[k % self.RING].tolist()
+            row = self.stats_host[k % self.RING].tolist()
+            norm, clipped, skipped, err = row[:4]
             rec = (norm, bool(clipped), bool(skipped), bool(err))
             done.append(rec)
             self.history.append(rec)
@@ -129,6 +145,8 @@ class FusedClipAdam(object):
                 if self.hook.gstats is None:
                     self.hook.gstats = _NormStats()
                 self.hook.gstats.add(norm, int(rec[1]), int(rec[2]))
+            if self.kill_on_nan is not None:
+                self.kill_on_nan.device_record(row[4] != 0)       # SystemExit(1) on the 10th
         return done
 
     def drain(self):

@@ -13,7 +13,8 @@
 //     updates its chunk of parameters: m, v (flat, owned by the caller) and the
 //     parameter tensors themselves through a chunk table (the parameters stay where
 //     torch allocated them).  Block 0 leaves {norm, clipped, skipped, step} for the
-//     host to read whenever it likes.
+//     host to read whenever it likes (asr_adam_clip_step_ex_f32: a fifth entry, the caller's
+//     skip word, which is OR-ed into the skip decision).
 // HBM-bound: 7 floats per parameter element.
 #include "common.h"
 #include "../../include/asr_amd.h"
@@ -46,6 +47,7 @@ struct AdamParams {
     const float *partials;
     int nparts, nchunks;
     const uint32_t *err;
+    const uint32_t *skip_word;      // NULL: no extra skip request (asr_adam_clip_step_f32)
     float lr, beta1, beta2, eps, wd, clip, skip;
     const int32_t *step_in;
     int32_t *step_out;
@@ -62,7 +64,8 @@ __global__ __launch_bounds__(TPB) void adam_clip_step_kernel(AdamParams p) {
     if (threadIdx.x == 0) {
         const float norm = sqrtf(s);
         const bool err = p.err && *p.err != 0u;
-        const bool skip = !(norm <= p.skip) || !isfinite(norm) || err;      // NaN: skip
+        const bool ext = p.skip_word && *p.skip_word != 0u;                 // e.g. KillOnNan's flag
+        const bool skip = !(norm <= p.skip) || !isfinite(norm) || err || ext;   // NaN: skip
         const float coef = p.clip / (norm + 1e-6f);                          // clip_grad_norm_'s rule
         const int t = *p.step_in + 1;
         // bias corrections as torch computes them (Python doubles)
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(TPB) void adam_clip_step_kernel(AdamParams p) {
             p.stats[1] = coef < 1.f ? 1.f : 0.f;
             p.stats[2] = skip ? 1.f : 0.f;
             p.stats[3] = err ? 1.f : 0.f;
+            if (p.skip_word) p.stats[4] = ext ? 1.f : 0.f;
             *p.step_out = skip ? t - 1 : t;
         }
     }
@@ -140,22 +144,34 @@ extern "C" int asr_grad_sumsq_partials_f32(const float *g, int64_t n, float *par
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
 }
 
-extern "C" int asr_adam_clip_step_f32(const AsrAdamChunk *chunks, int nchunks, const float *g_flat,
-                                      float *m_flat, float *v_flat, const float *partials, int nparts,
-                                      const uint32_t *err_word, float lr, float beta1, float beta2,
-                                      float eps, float weight_decay, float clip_norm,
-                                      float skip_norm, const int32_t *step_in, int32_t *step_out,
-                                      float *stats, void *stream) {
+extern "C" int asr_adam_clip_step_ex_f32(const AsrAdamChunk *chunks, int nchunks, const float *g_flat,
+                                         float *m_flat, float *v_flat, const float *partials, int nparts,
+                                         const uint32_t *err_word, float lr, float beta1, float beta2,
+                                         float eps, float weight_decay, float clip_norm,
+                                         float skip_norm, const int32_t *step_in, int32_t *step_out,
+                                         const uint32_t *skip_word, float *stats, void *stream) {
     if (!chunks || nchunks <= 0 || !g_flat || !m_flat || !v_flat || !partials || nparts <= 0 ||
         !step_in || !step_out || step_in == step_out || !stats)
         return ASR_EINVAL;
     AdamParams p;
     p.chunks = chunks; p.g = g_flat; p.m = m_flat; p.v = v_flat;
     p.partials = partials; p.nparts = nparts; p.nchunks = nchunks; p.err = err_word;
+    p.skip_word = skip_word;
     p.lr = lr; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps; p.wd = weight_decay;
     p.clip = clip_norm; p.skip = skip_norm;
     p.step_in = step_in; p.step_out = step_out; p.stats = stats;
     hipLaunchKernelGGL(adam_clip_step_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(TPB), 0,
                        (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+}
+
+extern "C" int asr_adam_clip_step_f32(const AsrAdamChunk *chunks, int nchunks, const float *g_flat,
+                                      float *m_flat, float *v_flat, const float *partials, int nparts,
+                                      const uint32_t *err_word, float lr, float beta1, float beta2,
+                                      float eps, float weight_decay, float clip_norm,
+                                      float skip_norm, const int32_t *step_in, int32_t *step_out,
+                                      float *stats, void *stream) {
+    return asr_adam_clip_step_ex_f32(chunks, nchunks, g_flat, m_flat, v_flat, partials, nparts,
+                                     err_word, lr, beta1, beta2, eps, weight_decay, clip_norm,
+                                     skip_norm, step_in, step_out, nullptr, stats, stream);
 }
