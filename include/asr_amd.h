@@ -519,6 +519,39 @@ int asr_tcn_attention_step_f32(const float *eproj, const float *enc, const int32
                                float *att_new, float *context, void *stream);
 
 /*
+ * The training recurrence of the same local attention over all label positions (ABI v24;
+ * replaces the per-position loop of AttentionDecoderTCN.forward, reference
+ * att_speech/modules/tcn.py:357-440, over LocalAttention.scores / forward, :190-230, and the
+ * backward pass autograd replays through it).  One workgroup per utterance for the whole scan.
+ *   eproj  [T, B, A]     encoded_to_hidden(encoded), time-major
+ *   filt   [L, B, A*Kf]  lm_to_kernel(lm_states): the Kf = 32 taps of one unit contiguous
+ *   glob   [L, B, A]     lm_to_global(lm_states)
+ *   a0     [T, B]        the initial alignment a_{-1} (init_attention)
+ *   w_score [A], b_score [1] (device memory): hidden_to_score;  enc_lens [B] int32
+ *   fwd: att [L, B, T]   a_l = softmax_t( temperature * (w . tanh(eproj_t + glob_l +
+ *                        sum_j a_{l-1}[t-(Kf-1)+j] filt_l[., j]) + b) + pad_t ), the previous
+ *                        alignment left-padded with zeros; pad_t = -1e5 for t >= enc_lens[b]
+ *   bwd: d_att [L, B, T] the gradient reaching each a_l from outside the recurrence; the
+ *                        gradients of the inputs: d_eproj [T, B, A], d_filt [L, B, A*Kf],
+ *                        d_glob [L, B, A], d_a0 [T, B], and per-utterance partials
+ *                        d_wb [B, A+1] of d w_score (A entries) and d b_score (the last one;
+ *                        zero up to rounding, the softmax being shift-invariant).
+ * h is recomputed in the backward pass; nothing but att is saved.  Every reduction has a
+ * fixed owner and order: the results are bitwise reproducible.  Limits: Kf == 32,
+ * 1 <= A <= 256, 1 <= T <= 4096 (ASR_EUNSUPPORTED beyond), L >= 1, B >= 1.
+ */
+int asr_tcn_attention_scan_fwd_f32(const float *eproj, const float *filt, const float *glob,
+                                   const float *a0, const float *w_score, const float *b_score,
+                                   float temperature, const int32_t *enc_lens, int T, int B,
+                                   int L, int A, int Kf, float *att, void *stream);
+int asr_tcn_attention_scan_bwd_f32(const float *eproj, const float *filt, const float *glob,
+                                   const float *a0, const float *w_score, float temperature,
+                                   const int32_t *enc_lens, const float *att, const float *d_att,
+                                   int T, int B, int L, int A, int Kf, float *d_eproj,
+                                   float *d_filt, float *d_glob, float *d_a0, float *d_wb,
+                                   void *stream);
+
+/*
  * One step of BeamSearch for every utterance, without a host read-back (replaces
  * BeamSearch.step + _save_best_finished, reference att_speech/modules/beam_search.py:58-124,
  * 147-175).  logits [B*beam, C] (class C-1 = EOS); scores_in / scores_out [B*beam] running

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get(     # ASR_AMD_LIB: development override (kernel A/B b
     'ASR_AMD_LIB', os.path.join(os.path.dirname(_HERE), 'csrc', 'libasr_amd.so'))
 
 ASR_OK, ASR_EINVAL, ASR_EUNSUPPORTED, ASR_ELAUNCH = 0, 1, 2, 3
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _lib = None
 # bench.py sets this to a list to collect (start, end) torch.cuda.Event pairs
@@ -77,6 +77,9 @@ _SIGNATURES = {
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),
     'asr_tcn_attention_step_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp,
                                         _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'asr_tcn_attention_scan_fwd_f32': (_i, [_vp] * 6 + [_f, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'asr_tcn_attention_scan_bwd_f32': (_i, [_vp] * 5 + [_f, _vp, _vp, _vp, _i, _i, _i, _i, _i] +
+                                       [_vp] * 6),
     'asr_beam_step_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'asr_ctc_graph_build': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f] + [_vp] * 8),
@@ -875,6 +878,45 @@ def tcn_attention_step(eproj, enc, enc_lens, filt, glob, w_score, b_score, tempe
         float(temperature), _p(att_prev), _p(par), T, B, beam, A, taps, E, _p(att_new), _p(ctx),
         _stream()), 'asr_tcn_attention_step_f32')
     return att_new, ctx
+
+
+def tcn_attention_scan_fwd(eproj, filt, glob, a0, w_score, b_score, enc_lens, temperature):
+    """asr_tcn_attention_scan_fwd_f32 -> every alignment of the training scan [L, B, T]."""
+    eproj, a0 = _dev(eproj, torch.float32, 'eproj'), _dev(a0, torch.float32, 'a0')
+    filt, glob = _dev(filt, torch.float32, 'filt'), _dev(glob, torch.float32, 'glob')
+    w_score = _dev(w_score, torch.float32, 'w_score')
+    b_score = _dev(b_score, torch.float32, 'b_score')
+    enc_lens = _dev(enc_lens, torch.int32, 'enc_lens')
+    T, B, A = eproj.shape
+    L = glob.shape[0]
+    att = torch.empty((L, B, T), dtype=torch.float32, device=eproj.device)
+    check(lib().asr_tcn_attention_scan_fwd_f32(
+        _p(eproj), _p(filt), _p(glob), _p(a0), _p(w_score), _p(b_score), float(temperature),
+        _p(enc_lens), T, B, L, A, filt.shape[2] // A, _p(att), _stream()),
+        'asr_tcn_attention_scan_fwd_f32')
+    return att
+
+
+def tcn_attention_scan_bwd(eproj, filt, glob, a0, w_score, enc_lens, temperature, att, d_att):
+    """asr_tcn_attention_scan_bwd_f32 -> (d_eproj [T, B, A], d_filt [L, B, A*Kf],
+    d_glob [L, B, A], d_a0 [T, B], d_wb [B, A+1] per-utterance partials of d w / d b)."""
+    eproj, a0 = _dev(eproj, torch.float32, 'eproj'), _dev(a0, torch.float32, 'a0')
+    filt, glob = _dev(filt, torch.float32, 'filt'), _dev(glob, torch.float32, 'glob')
+    w_score = _dev(w_score, torch.float32, 'w_score')
+    enc_lens = _dev(enc_lens, torch.int32, 'enc_lens')
+    att, d_att = _dev(att, torch.float32, 'att'), _dev(d_att, torch.float32, 'd_att')
+    T, B, A = eproj.shape
+    L = glob.shape[0]
+    d_eproj = torch.empty_like(eproj)
+    d_filt = torch.empty_like(filt)
+    d_glob = torch.empty_like(glob)
+    d_a0 = torch.empty_like(a0)
+    d_wb = torch.empty((B, A + 1), dtype=torch.float32, device=eproj.device)
+    check(lib().asr_tcn_attention_scan_bwd_f32(
+        _p(eproj), _p(filt), _p(glob), _p(a0), _p(w_score), float(temperature), _p(enc_lens),
+        _p(att), _p(d_att), T, B, L, A, filt.shape[2] // A, _p(d_eproj), _p(d_filt), _p(d_glob),
+        _p(d_a0), _p(d_wb), _stream()), 'asr_tcn_attention_scan_bwd_f32')
+    return d_eproj, d_filt, d_glob, d_a0, d_wb
 
 
 def beam_step(logits, scores_in, scores_out, est_in, est_out, step, B, beam, len_div, state):

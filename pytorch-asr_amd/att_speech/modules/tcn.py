@@ -222,6 +222,39 @@ class LocalAttention(nn.Module):
         return att_state, rows.t()
 
 
+_SCAN_MAX_FRAMES = 4096     # asr_tcn_attention_scan_*_f32: longest encoder sequence
+_SCAN_MAX_WIDTH = 256       # ... and widest attention
+
+
+class _AttentionScan(torch.autograd.Function):
+    """The whole training recurrence of LocalAttention over the label positions as one
+    autograd node: asr_tcn_attention_scan_fwd_f32 forward, asr_tcn_attention_scan_bwd_f32
+    backward (h recomputed, only the alignments saved).
+    eproj [T', B, A], filt [L, B, A*K], glob [L, B, A], a0 [T', B], w_score [A],
+    b_score [1] -> alignments [L, B, T']."""
+
+    @staticmethod
+    def forward(ctx, eproj, filt, glob, a0, w_score, b_score, lens, temperature):
+        from att_speech import _native
+        eproj, filt, glob = eproj.contiguous(), filt.contiguous(), glob.contiguous()
+        a0, w_score = a0.contiguous(), w_score.contiguous()
+        att = _native.tcn_attention_scan_fwd(eproj, filt, glob, a0, w_score, b_score, lens,
+                                             temperature)
+        ctx.save_for_backward(eproj, filt, glob, a0, w_score, lens, att)
+        ctx.temperature = temperature
+        return att
+
+    @staticmethod
+    def backward(ctx, d_att):
+        from att_speech import _native
+        eproj, filt, glob, a0, w_score, lens, att = ctx.saved_tensors
+        d_eproj, d_filt, d_glob, d_a0, d_wb = _native.tcn_attention_scan_bwd(
+            eproj, filt, glob, a0, w_score, lens, ctx.temperature, att, d_att.contiguous())
+        A = w_score.numel()
+        d_wb = d_wb.sum(0)
+        return (d_eproj, d_filt, d_glob, d_a0, d_wb[:A], d_wb[A:], None, None)
+
+
 _SMOOTHING_TAPS = (0.005, 0.02, 0.95, 0.02, 0.005)      # along the label axis (:411-414)
 
 
@@ -311,6 +344,34 @@ class AttentionDecoderTCN(nn.Module):
         dist[:, :, 0] = 0
         return dist
 
+    def _native_train_ok(self, encoded):
+        """The training recurrence through asr_tcn_attention_scan_*_f32 (read per call;
+        ASR_TCN_TRAIN_NATIVE=0 keeps the per-position loop)."""
+        if os.environ.get('ASR_TCN_TRAIN_NATIVE', '1') == '0':
+            return False
+        attn = self.attn
+        return (encoded.is_cuda and encoded.dtype == torch.float32
+                and attn.kernel_size == 32 and not attn.force_forward
+                and 1 <= encoded.size(0) <= _SCAN_MAX_FRAMES
+                and 1 <= self.att_hidden_size <= _SCAN_MAX_WIDTH)
+
+    def _forward_scan(self, encoded, encoded_lens, lm_states, eproj, first):
+        """All L positions at once: the filter / global LM terms as one product each, the
+        alignment recurrence as ONE autograd node (_AttentionScan), every context as one
+        batched product and the output MLP once over [B, L, .] -> (alignments [L, B, T'],
+        logits [B, L, C]).  In training mode the MLP's
+        dropout masks are drawn in that one call (same distribution, another RNG stream)."""
+        attn = self.attn
+        lens = torch.as_tensor(encoded_lens).to(encoded.device, torch.int32)
+        filt = attn.lm_to_kernel(lm_states)                                    # [L, B, A*K]
+        glob = attn.lm_to_global(lm_states)                                    # [L, B, A]
+        att = _AttentionScan.apply(eproj, filt, glob, first,
+                                   attn.hidden_to_score.weight.reshape(-1),
+                                   attn.hidden_to_score.bias, lens, attn.temperature)
+        contexts = torch.bmm(att.transpose(0, 1), encoded.transpose(0, 1))     # [B, L, E]
+        logits = self._step_output(lm_states.transpose(0, 1), contexts)        # [B, L, C]
+        return att, logits
+
     def forward(self, encoded, encoded_lens, texts, text_lens,
                 return_att_weights=False, **kwargs):
         """Teacher-forced loss (:357-440): the TCN reads <start> + labels, every label
@@ -326,13 +387,18 @@ class AttentionDecoderTCN(nn.Module):
         lm_states = self.tcn(torch.cat((torch.zeros_like(history[:1]), history[:-1])))
         att_state, alignment = self.attn.init_attention(encoded, encoded_lens)
         enc_rows = encoded.transpose(0, 1)                                     # [B, T', E]
-        alignments, step_logits = [], []
-        for lm_state in lm_states:
-            att_state, alignment = self.attn(att_state, lm_state, alignment)
-            alignments.append(alignment)
-            context = torch.bmm(alignment.t().unsqueeze(1), enc_rows).squeeze(1)
-            step_logits.append(self._step_output(lm_state, context))
-        logits = torch.stack(step_logits, 1)                                   # [B, L, C]
+        if self._native_train_ok(encoded):
+            att, logits = self._forward_scan(encoded, encoded_lens, lm_states, att_state[0],
+                                             alignment)
+            alignments = [a.t() for a in att.unbind(0)] if return_att_weights else None
+        else:
+            alignments, step_logits = [], []
+            for lm_state in lm_states:
+                att_state, alignment = self.attn(att_state, lm_state, alignment)
+                alignments.append(alignment)
+                context = torch.bmm(alignment.t().unsqueeze(1), enc_rows).squeeze(1)
+                step_logits.append(self._step_output(lm_state, context))
+            logits = torch.stack(step_logits, 1)                               # [B, L, C]
         targets = self._smoothed_targets(labels)
         per_position = -(F.log_softmax(logits, 2) * targets).sum(2)
         loss = per_position.mean() / targets.sum(2).mean()
