@@ -340,6 +340,48 @@ int asr_lstm_bidir_bwd_bf16(const float *dy, int dy_shared, const void *whhT_bf1
                             uint32_t *err_flag, void *stream);
 
 /*
+ * Bidirectional GRU recurrence (bias-free; the recurrent part of a BatchRNN with
+ * rnn_type=nn.GRU), the arithmetic of torch.nn.GRU(bias=False) with rows in torch's order
+ * r | z | n:
+ *   r = σ(gx_r + h·W_hrᵀ)   z = σ(gx_z + h·W_hzᵀ)   hn = h·W_hnᵀ
+ *   n = tanh(gx_n + r ⊙ hn)  h' = (1 − z) ⊙ n + z ⊙ h
+ * Same contract as the LSTM above: padded input with lens[B] (utterance b is active at
+ * frame t iff t < lens[b]; padding frames emit zeros and carry no gradient; the reverse
+ * direction starts from the zero state at each utterance's own last frame); bf16 MFMA
+ * operands (h, W_hh), fp32 accumulation, gates and state; persistent kernels by default,
+ * one launch per step with ASR_LSTM_PERSIST=0 (bit-identical); err_flag and
+ * ASR_LSTM_SPIN_LIMIT as for the LSTM.
+ *   gx [T,B,2,3H] f32, or bf16 with gx_bf16 != 0: x · W_ihᵀ per direction (gate order r,z,n)
+ *   whh [2,3H,H] bf16 for the forward pass, whhT [2,H,3H] (transposed) for the backward pass
+ *   y      [T,B,2,H] f32 per-direction outputs (required: the backward pass reads h_{t-1}
+ *                    from it)
+ *   y_bf16 [2,T+2,B,H] bf16 copy laid out as the LSTM's (h_{t-1} operands for dW_hh)
+ *   gates_bf16 [T,2,B,H,4] bf16 records (r, z, n, hn) saved for the backward pass
+ *   dy     [T,B,2,H], or [T,B,H] with dy_shared != 0 (one gradient for both directions)
+ *   dgx_bf16 [T,B,2,3H] bf16 (dr, dz, dn) pre-activation gradients = gradient w.r.t. gx:
+ *                    the operand of dx and dW_ih
+ *   dhn_bf16 [T,B,2,H] bf16 dn ⊙ r: with dr, dz the operand [dr, dz, dhn] of dW_hh
+ * workspace: asr_gru_workspace_bytes(B, H) bytes.  Hidden sizes built: 64, 128, 256, 320
+ * (ASR_EUNSUPPORTED otherwise).  asr_gru_supported(B, H): 0 = not built; bit 0 = runs;
+ * bit 1 = the persistent kernels take this shape (else one launch per step).
+ */
+int64_t asr_gru_workspace_bytes(int B, int H);
+int asr_gru_supported(int B, int H);
+
+int asr_gru_bidir_fwd_bf16(const void *gx, int gx_bf16, const void *whh_bf16,
+                           const int32_t *lens, int T, int B, int H,
+                           float *y, void *y_bf16, void *gates_bf16,
+                           void *workspace, int64_t workspace_bytes,
+                           uint32_t *err_flag, void *stream);
+
+int asr_gru_bidir_bwd_bf16(const float *dy, int dy_shared, const void *whhT_bf16,
+                           const int32_t *lens, int T, int B, int H,
+                           const void *gates_bf16, const float *y,
+                           void *dgx_bf16, void *dhn_bf16,
+                           void *workspace, int64_t workspace_bytes,
+                           uint32_t *err_flag, void *stream);
+
+/*
  * BatchNorm2d + Hardtanh(lo, hi) fused over the [B, C, H, W] output of a
  * convolution (fp32, or bf16 with x_bf16 — channels-last only; dx then is bf16 too): the `Normalization('batch_norm')` + `nn.Hardtanh(0, 20)` pair of
  * the DeepSpeech2 conv front-end (deep_speech_2.py:60-73).  training != 0: batch

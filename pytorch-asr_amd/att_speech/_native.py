@@ -100,6 +100,10 @@ _SIGNATURES = {
     'asr_lstm_wgrad_workspace_bytes': (_i64, [_i, _i, _i, _i]),
     'asr_lstm_wgrad_bf16': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     'asr_lstm_bidir_fwd_fused_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    'asr_gru_workspace_bytes': (_i64, [_i, _i]),
+    'asr_gru_supported': (_i, [_i, _i]),
+    'asr_gru_bidir_fwd_bf16': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    'asr_gru_bidir_bwd_bf16': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'asr_bn_act_workspace_bytes': (_i64, [_i]),
     'asr_bn_act_fwd_f32': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f,
                                 _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -456,14 +460,14 @@ def lstm_error_word(device):
 def lstm_raise_error(word):
     word.zero_()
     raise RuntimeError(
-        'persistent BiLSTM recurrence: a team hand-off timed out (another stream\'s kernel kept a '
+        'persistent BiLSTM / BiGRU recurrence: a team hand-off timed out (another stream\'s kernel kept a '
         'team mate off the device?); the outputs of that call, and the gradients of this step on '
         'every rank, are NaN: the step is discarded. Set ASR_LSTM_PERSIST=0 to use one launch per '
         'time step.')
 
 
 def lstm_check_errors():
-    """Raise if a hand-off of the persistent BiLSTM recurrence timed out since the last
+    """Raise if a hand-off of the persistent BiLSTM / BiGRU recurrence timed out since the last
     check (csrc/lstm.hip team_wait: the kernel then poisons its outputs with NaN; the
     step must be discarded).  One 4-byte read-back per device; `dp.train_step` calls it
     once per step."""
@@ -471,7 +475,7 @@ def lstm_check_errors():
         if int(f.item()) != 0:
             f.zero_()
             raise RuntimeError(
-                'persistent BiLSTM recurrence: a team hand-off timed out on cuda:%d (another '
+                'persistent BiLSTM / BiGRU recurrence: a team hand-off timed out on cuda:%d (another '
                 "stream's kernel kept a team mate off the device?); outputs of that call are "
                 'NaN. Set ASR_LSTM_PERSIST=0 to use one launch per time step.' % idx)
 
@@ -664,6 +668,59 @@ def lstm_bidir_bwd_fused(dy, whhT_bf16, wihT_bf16, lens, gates, csave, planes=Fa
                                           _p(_lstm_err_flag(dy.device)), _stream()),
           'asr_lstm_bidir_bwd_fused_bf16')
     return dgates, dx
+
+
+def gru_supported(B, H):
+    """asr_gru_supported: is the GRU recurrence built for this (batch, hidden size)?"""
+    return bool(lib().asr_gru_supported(int(B), int(H)) & 1)
+
+
+def gru_bidir_fwd(gx, whh_bf16, lens):
+    """asr_gru_bidir_fwd_bf16: gx [T,B,2,3H] f32 or bf16, whh [2,3H,H] bf16, lens [B] i32
+    -> (y [T,B,2,H] f32, y_bf16 [2,T+2,B,H], gates [T,2,B,H,4] bf16 records (r, z, n, hn)).
+    Shares the LSTM's error word (lstm_check_errors)."""
+    gx = _dev(gx, gx.dtype if gx.dtype == torch.bfloat16 else torch.float32, 'gx')
+    whh_bf16 = _dev(whh_bf16, torch.bfloat16, 'whh')
+    lens = _dev(lens, torch.int32, 'lens')
+    T, B, _, H3 = gx.shape
+    H = H3 // 3
+    if tuple(whh_bf16.shape) != (2, 3 * H, H):
+        raise ValueError('gru_bidir_fwd: whh must be [2, 3H, H]')
+    L = lib()
+    dev = gx.device
+    y = torch.empty((T, B, 2, H), dtype=torch.float32, device=dev)
+    ybf = torch.empty((2, T + 2, B, H), dtype=torch.bfloat16, device=dev)
+    gates = torch.empty((T, 2, B, H, 4), dtype=torch.bfloat16, device=dev)
+    nbytes = L.asr_gru_workspace_bytes(B, H)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.asr_gru_bidir_fwd_bf16(_p(gx), int(gx.dtype == torch.bfloat16), _p(whh_bf16), _p(lens),
+                                   T, B, H, _p(y), _p(ybf), _p(gates), _p(ws), nbytes,
+                                   _p(_lstm_err_flag(dev)), _stream()), 'asr_gru_bidir_fwd_bf16')
+    return y, ybf, gates
+
+
+def gru_bidir_bwd(dy, whhT_bf16, lens, gates, y):
+    """asr_gru_bidir_bwd_bf16 -> (dgx [T,B,2,3H] bf16 = (dr, dz, dn), dhn [T,B,2,H] bf16).
+    dy [T,B,2,H], or [T,B,H] when the two directions share one gradient; whhT [2,H,3H] bf16;
+    gates, y: what gru_bidir_fwd returned."""
+    dy = _dev(dy, torch.float32, 'dy')
+    whhT_bf16 = _dev(whhT_bf16, torch.bfloat16, 'whhT')
+    lens = _dev(lens, torch.int32, 'lens')
+    gates = _dev(gates, torch.bfloat16, 'gates')
+    y = _dev(y, torch.float32, 'y')
+    T, B, H = dy.shape[0], dy.shape[1], dy.shape[-1]
+    if tuple(whhT_bf16.shape) != (2, H, 3 * H) or tuple(y.shape) != (T, B, 2, H):
+        raise ValueError('gru_bidir_bwd: whhT must be [2, H, 3H], y [T, B, 2, H]')
+    L = lib()
+    dev = dy.device
+    dgx = torch.empty((T, B, 2, 3 * H), dtype=torch.bfloat16, device=dev)
+    dhn = torch.empty((T, B, 2, H), dtype=torch.bfloat16, device=dev)
+    nbytes = L.asr_gru_workspace_bytes(B, H)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.asr_gru_bidir_bwd_bf16(_p(dy), int(dy.dim() == 3), _p(whhT_bf16), _p(lens), T, B, H,
+                                   _p(gates), _p(y), _p(dgx), _p(dhn), _p(ws), nbytes,
+                                   _p(_lstm_err_flag(dev)), _stream()), 'asr_gru_bidir_bwd_bf16')
+    return dgx, dhn
 
 
 class GroupedGraph(object):

@@ -80,15 +80,16 @@ class BatchRNN(nn.Module):
         self.rnn.flatten_parameters()
 
     def _use_native(self, x):
-        # the MI355X path: hand-written recurrence kernels (csrc/lstm.hip)
-        native = (isinstance(self.rnn, nn.LSTM) and self.bidirectional
-                  and self.hidden_size in (64, 128, 256, 320, 384, 512, 768)
-                  and not self.rnn.bias)
+        # the MI355X path: hand-written recurrence kernels (csrc/lstm.hip, csrc/gru.hip)
+        built = (64, 128, 256, 320, 384, 512, 768) if isinstance(self.rnn, nn.LSTM) else \
+            (64, 128, 256, 320) if isinstance(self.rnn, nn.GRU) else ()
+        native = (self.bidirectional and self.hidden_size in built and not self.rnn.bias)
         if x.is_cuda and not native and not getattr(self, '_warned', False):
             self._warned = True
             warnings.warn(
                 'BatchRNN(%s, hidden %d, bidirectional=%s): no hand-written recurrence for this '
-                'layer (built: bias-free bidirectional LSTM, hidden 64/128/256/320/384/512/768); '
+                'layer (built: bias-free bidirectional LSTM, hidden 64/128/256/320/384/512/768; '
+                'bias-free bidirectional GRU, hidden 64/128/256/320); '
                 'running torch nn.%s (MIOpen) instead' % (
                     type(self.rnn).__name__, self.hidden_size, self.bidirectional,
                     type(self.rnn).__name__))
@@ -108,15 +109,18 @@ class BatchRNN(nn.Module):
             x[mask] = self.batch_norm(flat)
         summed = False
         if self._use_native(x):
-            from att_speech.modules.encoders.native_lstm import bilstm
+            if isinstance(self.rnn, nn.GRU):
+                from att_speech.modules.encoders.native_gru import bigru as native_rnn
+            else:
+                from att_speech.modules.encoders.native_lstm import bilstm as native_rnn
             # the direction sum of :112-117 happens inside the function when nothing
-            # sits between the LSTM and the merge
+            # sits between the recurrence and the merge
             summed = self.projection is None and not self.subsample
-            y = bilstm(x, lens_t, self.rnn, sum_dirs=summed)
+            y = native_rnn(x, lens_t, self.rnn, sum_dirs=summed)
             y = y if summed else y.view(T, B, -1)               # [T,B,2H], zeros on padding
         else:
-            # host / non-LSTM evaluation with stock torch ops (CPU reference in
-            # the tests and bench.py's cpu_baseline; GRU layers)
+            # host evaluation / layers without a native recurrence, with stock torch ops
+            # (CPU reference in the tests and bench.py's cpu_baseline)
             packed = nn.utils.rnn.pack_padded_sequence(x, lens_t.cpu())
             y, _ = self.rnn(packed)
             y, _ = nn.utils.rnn.pad_packed_sequence(y, total_length=T)
@@ -138,10 +142,12 @@ class SequentialWithOptionalAttributes(nn.Sequential):
 
     def _plain_native_stack(self, x):
         """every module a BatchRNN that is nothing but a native bidirectional LSTM with summed
-        directions: the whole stack runs as one autograd node (native_lstm.bilstm_stack)"""
+        directions: the whole stack runs as one autograd node (native_lstm.bilstm_stack; GRU
+        layers run one by one)"""
         mods = list(self._modules.values())
         return len(mods) > 1 and all(
-            isinstance(m, BatchRNN) and m._use_native(x) and m.projection is None
+            isinstance(m, BatchRNN) and isinstance(m.rnn, nn.LSTM) and m._use_native(x)
+            and m.projection is None
             and not m.subsample and not m.residual
             and isinstance(m.batch_norm.batch_norm, Identity) for m in mods)
 
