@@ -594,6 +594,60 @@ int asr_tcn_attention_scan_bwd_f32(const float *eproj, const float *filt, const 
                                    void *stream);
 
 /*
+ * The label scan of the RNN attention decoder (an addition to ABI v24; replaces the
+ * per-position loop of AttentionDecoderRNN.forward, reference att_speech/modules/decoders/
+ * attention_decoder.py:217-232 over Attention.forward :90-111, one nn.GRU step per position,
+ * and, with L = 1, one label step of .decode :324-337).  Per hypothesis b and position l:
+ *   rec_l = w_rec h_{l-1}
+ *   a_l   = softmax_t( w_score . tanh(eproj_t + rec_l) + b_score + pad_t ),
+ *           pad_t = -1e5 for t >= enc_lens: those frames get exactly 0
+ *   c_l   = sum_t a_l[t] encoded_t
+ *   gi = gx_emb_l + w_ic c_l,  gh = w_hh h_{l-1} + b_hh            (gate order r, z, n)
+ *   r = σ(gi_r + gh_r)  z = σ(gi_z + gh_z)  n = tanh(gi_n + r ⊙ gh_n)  h_l = (1−z) ⊙ n + z ⊙ h_{l-1}
+ * One workgroup per hypothesis for the whole scan; fp32 throughout.
+ *   eproj   [T, B/beam, A]  encoded_to_hidden(encoded) (bias included), time-major
+ *   encoded [T, B/beam, E];  enc_lens [B/beam] int32: hypothesis b reads utterance b / beam
+ *   gx_emb  [L, B, 3H]      embedding half of W_ih x + b_ih (b_ih included)
+ *   w_ic [3H, E] context half of W_ih;  w_hh [3H, H];  b_hh [3H];  w_rec [A, H]
+ *   w_score [A], b_score [1] (device memory);  h0 [B, H]
+ *   fwd out: att [L, B, T], states [L, B, H]; for the backward pass (each may be null):
+ *            contexts [L, B, E], gates [L, B, 4H] = one record (r, z, n, gh_n) per unit,
+ *            rec [L, B, A]
+ *   bwd (beam = 1): w_icT [E, 3H], w_hhT [H, 3H], w_recT [H, A] are the transposes;
+ *            d_att [L, B, T] and d_states [L, B, H] are the gradients reaching the outputs
+ *            from outside the recurrence (either may be null = zero).  Written:
+ *            d_eproj [T, B, A]   ACCUMULATED: the caller zero-fills it
+ *            d_gates [L, B, 4H]  (dr, dz, dn, dn ⊙ r) pre-activation gradients: the first 3H
+ *                                are d gx_emb and the operand of d w_ic (with contexts); dr,
+ *                                dz, dn ⊙ r are d b_hh's terms and the operand of d w_hh
+ *                                (with h_{l-1})
+ *            d_contexts [L, B, E]  operand of d encoded = sum_l a_l ⊗ d c_l
+ *            d_rec [L, B, A]     operand of d w_rec (with h_{l-1})
+ *            d_w_score [B, A]    per-hypothesis partials of d w_score (d b_score is zero:
+ *                                the softmax is shift-invariant)
+ *            d_h0 [B, H]
+ * The alignment itself is not carried from position to position (only the reference's
+ * force_forward window reads the previous one; that option stays outside these kernels), so
+ * there is no initial-alignment operand.  Every reduction has a fixed owner and order: the
+ * results are bitwise reproducible.  Limits: 1 <= T <= 4096, A <= 320, H <= 320, E <= 512,
+ * A, E and H multiples of 4 (ASR_EUNSUPPORTED beyond); L >= 1, B >= 1, beam >= 1 dividing B.
+ */
+int asr_att_gru_scan_fwd_f32(const float *eproj, const float *encoded, const int32_t *enc_lens,
+                             const float *gx_emb, const float *w_ic, const float *w_hh,
+                             const float *b_hh, const float *w_rec, const float *w_score,
+                             const float *b_score, const float *h0, int T, int B, int beam,
+                             int L, int A, int E, int H, float *att, float *states,
+                             float *contexts, float *gates, float *rec, void *stream);
+int asr_att_gru_scan_bwd_f32(const float *eproj, const float *encoded, const int32_t *enc_lens,
+                             const float *w_icT, const float *w_hhT, const float *w_recT,
+                             const float *w_score, const float *h0, const float *att,
+                             const float *states, const float *gates, const float *rec,
+                             const float *d_att, const float *d_states, int T, int B, int L,
+                             int A, int E, int H, float *d_eproj, float *d_gates,
+                             float *d_contexts, float *d_rec, float *d_w_score, float *d_h0,
+                             void *stream);
+
+/*
  * One step of BeamSearch for every utterance, without a host read-back (replaces
  * BeamSearch.step + _save_best_finished, reference att_speech/modules/beam_search.py:58-124,
  * 147-175).  logits [B*beam, C] (class C-1 = EOS); scores_in / scores_out [B*beam] running

@@ -80,6 +80,8 @@ _SIGNATURES = {
     'asr_tcn_attention_scan_fwd_f32': (_i, [_vp] * 6 + [_f, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'asr_tcn_attention_scan_bwd_f32': (_i, [_vp] * 5 + [_f, _vp, _vp, _vp, _i, _i, _i, _i, _i] +
                                        [_vp] * 6),
+    'asr_att_gru_scan_fwd_f32': (_i, [_vp] * 11 + [_i] * 7 + [_vp] * 6),
+    'asr_att_gru_scan_bwd_f32': (_i, [_vp] * 14 + [_i] * 6 + [_vp] * 7),
     'asr_beam_step_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'asr_ctc_graph_build': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f] + [_vp] * 8),
@@ -974,6 +976,82 @@ def tcn_attention_scan_bwd(eproj, filt, glob, a0, w_score, enc_lens, temperature
         _p(att), _p(d_att), T, B, L, A, filt.shape[2] // A, _p(d_eproj), _p(d_filt), _p(d_glob),
         _p(d_a0), _p(d_wb), _stream()), 'asr_tcn_attention_scan_bwd_f32')
     return d_eproj, d_filt, d_glob, d_a0, d_wb
+
+
+ATT_GRU_MAX_FRAMES, ATT_GRU_MAX_HIDDEN, ATT_GRU_MAX_ENCODED = 4096, 320, 512
+
+
+def att_gru_supported(T, A, E, H):
+    """The limits of asr_att_gru_scan_*_f32 (include/asr_amd.h)."""
+    return (1 <= T <= ATT_GRU_MAX_FRAMES and 1 <= A <= ATT_GRU_MAX_HIDDEN
+            and 1 <= H <= ATT_GRU_MAX_HIDDEN and 1 <= E <= ATT_GRU_MAX_ENCODED
+            and A % 4 == 0 and E % 4 == 0 and H % 4 == 0)
+
+
+def att_gru_scan_fwd(eproj, encoded, enc_lens, gx_emb, w_ic, w_hh, b_hh, w_rec, w_score, b_score,
+                     h0, beam=1, save=True):
+    """asr_att_gru_scan_fwd_f32 -> (att [L, B, T], states [L, B, H], contexts [L, B, E],
+    gates [L, B, 4H], rec [L, B, A]); the last three are None with save=False."""
+    f32 = torch.float32
+    eproj, encoded = _dev(eproj, f32, 'eproj'), _dev(encoded, f32, 'encoded')
+    gx_emb, h0 = _dev(gx_emb, f32, 'gx_emb'), _dev(h0, f32, 'h0')
+    w_ic, w_hh, b_hh = _dev(w_ic, f32, 'w_ic'), _dev(w_hh, f32, 'w_hh'), _dev(b_hh, f32, 'b_hh')
+    w_rec, w_score = _dev(w_rec, f32, 'w_rec'), _dev(w_score, f32, 'w_score')
+    b_score = _dev(b_score, f32, 'b_score')
+    enc_lens = _dev(enc_lens, torch.int32, 'enc_lens')
+    T, NU, A = eproj.shape
+    E = encoded.shape[2]
+    L, B, H3 = gx_emb.shape
+    H = H3 // 3
+    if (encoded.shape[:2] != (T, NU) or B != NU * beam or h0.shape != (B, H) or H3 != 3 * H
+            or w_ic.shape != (H3, E) or w_hh.shape != (H3, H) or b_hh.numel() != H3
+            or w_rec.shape != (A, H) or w_score.numel() != A or enc_lens.numel() != NU):
+        raise AssertionError('asr_att_gru_scan_fwd_f32: inconsistent operand shapes')
+    new = lambda *shape: torch.empty(shape, dtype=f32, device=eproj.device)  # noqa: E731
+    att, states = new(L, B, T), new(L, B, H)
+    ctxs, gates, rec = (new(L, B, E), new(L, B, 4 * H), new(L, B, A)) if save else (None,) * 3
+    check(lib().asr_att_gru_scan_fwd_f32(
+        _p(eproj), _p(encoded), _p(enc_lens), _p(gx_emb), _p(w_ic), _p(w_hh), _p(b_hh), _p(w_rec),
+        _p(w_score), _p(b_score), _p(h0), T, B, beam, L, A, E, H, _p(att), _p(states), _p(ctxs),
+        _p(gates), _p(rec), _stream()), 'asr_att_gru_scan_fwd_f32')
+    return att, states, ctxs, gates, rec
+
+
+def att_gru_scan_bwd(eproj, encoded, enc_lens, w_icT, w_hhT, w_recT, w_score, h0, att, states,
+                     gates, rec, d_att, d_states):
+    """asr_att_gru_scan_bwd_f32 -> (d_eproj [T, B, A], d_gates [L, B, 4H], d_contexts [L, B, E],
+    d_rec [L, B, A], d_w_score partials [B, A], d_h0 [B, H]); d_att / d_states may be None."""
+    f32 = torch.float32
+    eproj, encoded = _dev(eproj, f32, 'eproj'), _dev(encoded, f32, 'encoded')
+    w_icT, w_hhT = _dev(w_icT, f32, 'w_icT'), _dev(w_hhT, f32, 'w_hhT')
+    w_recT, w_score = _dev(w_recT, f32, 'w_recT'), _dev(w_score, f32, 'w_score')
+    h0, att, states = _dev(h0, f32, 'h0'), _dev(att, f32, 'att'), _dev(states, f32, 'states')
+    gates, rec = _dev(gates, f32, 'gates'), _dev(rec, f32, 'rec')
+    d_att = None if d_att is None else _dev(d_att, f32, 'd_att')
+    d_states = None if d_states is None else _dev(d_states, f32, 'd_states')
+    enc_lens = _dev(enc_lens, torch.int32, 'enc_lens')
+    T, B, A = eproj.shape
+    E = encoded.shape[2]
+    L, _, H = states.shape
+    if (encoded.shape[:2] != (T, B) or states.shape[1] != B or att.shape != (L, B, T)
+            or gates.shape != (L, B, 4 * H) or rec.shape != (L, B, A) or h0.shape != (B, H)
+            or w_icT.shape != (E, 3 * H) or w_hhT.shape != (H, 3 * H) or w_recT.shape != (H, A)
+            or (d_att is not None and d_att.shape != att.shape)
+            or (d_states is not None and d_states.shape != states.shape)):
+        raise AssertionError('asr_att_gru_scan_bwd_f32: inconsistent operand shapes')
+    dev = eproj.device
+    d_eproj = torch.zeros_like(eproj)
+    d_gates = torch.empty_like(gates)
+    d_ctx = torch.empty((L, B, E), dtype=f32, device=dev)
+    d_rec = torch.empty_like(rec)
+    d_v = torch.empty((B, A), dtype=f32, device=dev)
+    d_h0 = torch.empty_like(h0)
+    check(lib().asr_att_gru_scan_bwd_f32(
+        _p(eproj), _p(encoded), _p(enc_lens), _p(w_icT), _p(w_hhT), _p(w_recT), _p(w_score),
+        _p(h0), _p(att), _p(states), _p(gates), _p(rec), _p(d_att), _p(d_states), T, B, L, A, E, H,
+        _p(d_eproj), _p(d_gates), _p(d_ctx), _p(d_rec), _p(d_v), _p(d_h0), _stream()),
+        'asr_att_gru_scan_bwd_f32')
+    return d_eproj, d_gates, d_ctx, d_rec, d_v, d_h0
 
 
 def beam_step(logits, scores_in, scores_out, est_in, est_out, step, B, beam, len_div, state):
