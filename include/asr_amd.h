@@ -776,6 +776,32 @@ int asr_noise_chunk_elems(void);
 int asr_gaussian_noise_f32(const AsrNoiseSegment *segs, int nsegs, uint64_t seed, uint32_t tag,
                            uint64_t iteration, int mode, int sign, void *stream);
 
+/*
+ * Batched Levenshtein distance with operation counts: the scoring of do_evaluate
+ * (att_speech/utils.py:35-65 `edit_distance_with_stats(x, y)`, called twice per utterance at
+ * utils.py:324-327, x = the hypothesis, y = the reference text).  These entry points are additions:
+ * no existing signature changes, so the ABI version stays 24.
+ *
+ * x, y: the token ids of all pairs, flat; pair p is x[x_off[p] : x_off[p+1]] against
+ * y[y_off[p] : y_off[p+1]] (x_off, y_off: n_pairs + 1 prefix offsets).  out [n_pairs, 4] =
+ * (dist, ins, del, sub) per pair.  dp[i][0] = i, dp[0][j] = j; a cell takes the minimum of
+ * (dp[i-1][j] + 1 "ins", dp[i][j-1] + 1 "del", dp[i-1][j-1] + (x != y) "sub") and the FIRST minimum
+ * in that order wins (np.argmin); the counts are those of the reference's trace-back along the
+ * chosen moves, a move counting only where the distance grows.  They are carried forward with the
+ * distance from the chosen predecessor (the same path read the other way), so no operation matrix
+ * is kept.  All results are exact integers; dist == ins + del + sub.
+ *
+ * max_x, max_y: upper bounds (host values) of the pairs' lengths; they size the launch.  A pair
+ * longer than the bounds it was launched with, or with decreasing offsets, gets (-1, -1, -1, -1).
+ * ASR_EINVAL before anything is launched: null pointers with n_pairs > 0, negative counts, or
+ * max_x / max_y above asr_edit_distance_max_len() (4096).  One wave per pair, no workspace, no
+ * atomics.
+ */
+int asr_edit_distance_max_len(void);
+int asr_edit_distance_stats_i32(const int32_t *x, const int32_t *x_off, const int32_t *y,
+                                const int32_t *y_off, int n_pairs, int max_x, int max_y,
+                                int32_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

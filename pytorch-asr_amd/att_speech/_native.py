@@ -72,6 +72,8 @@ _SIGNATURES = {
     'asr_nonfinite_flag_f32': (_i, [_vp, _i, _vp, _vp]),
     'asr_noise_chunk_elems': (_i, []),
     'asr_gaussian_noise_f32': (_i, [_vp, _i, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, _i, _i, _vp]),
+    'asr_edit_distance_max_len': (_i, []),
+    'asr_edit_distance_stats_i32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'asr_split_bf16_f32': (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     'asr_log_softmax_shift_bwd_split_blocks': (_i, [_i64]),
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),
@@ -1252,3 +1254,25 @@ def log_softmax_shift_bwd(y, nls, dy):
     check(lib().asr_log_softmax_shift_bwd_f32(_p(y), _p(nls), _p(dy), y.numel() // C, C, _p(dx),
                                               _stream()), 'asr_log_softmax_shift_bwd_f32')
     return dx
+
+
+def edit_distance_max_len():
+    """asr_edit_distance_max_len: the longest side asr_edit_distance_stats_i32 is built for."""
+    return int(lib().asr_edit_distance_max_len())
+
+
+def edit_distance_stats(x, x_off, y, y_off, max_x, max_y):
+    """asr_edit_distance_stats_i32: flat int32 token ids x, y with prefix offsets x_off, y_off
+    [n + 1] (all on the GPU; max_x, max_y: host bounds of the pairs' lengths) -> int32 [n, 4]
+    (dist, ins, del, sub) per pair.  Lengths above edit_distance_max_len() are refused
+    (AssertionError) before anything is launched."""
+    x, x_off = _dev(x, torch.int32, 'x'), _dev(x_off, torch.int32, 'x_off')
+    y, y_off = _dev(y, torch.int32, 'y'), _dev(y_off, torch.int32, 'y_off')
+    n = x_off.numel() - 1
+    if n < 0 or y_off.numel() != n + 1:
+        raise AssertionError('edit_distance_stats: x_off and y_off must both hold n + 1 offsets')
+    out = torch.empty((n, 4), dtype=torch.int32, device=x.device)
+    check(lib().asr_edit_distance_stats_i32(_p(x), _p(x_off), _p(y), _p(y_off), n, int(max_x),
+                                            int(max_y), _p(out), _stream()),
+          'asr_edit_distance_stats_i32')
+    return out

@@ -53,7 +53,8 @@ class PolyakDecay(TrainingLoopHook):
     def post_dev_eval(self, model, current_iteration, logger, save_dir, dev_dataset,
                       evaluate=None):
         """`evaluate(dev_dataset, model) -> dict` scores one model (the reference
-        calls utils.evaluate_greedy, which belongs to the out-of-scope dev loop)."""
+        calls utils.evaluate_greedy: pass `att_speech.utils.evaluate_greedy`; the default
+        stays None, which skips the evaluation)."""
         if evaluate is None:
             return
         old_state = deepcopy(model.state_dict())
