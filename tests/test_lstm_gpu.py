@@ -53,7 +53,9 @@ def test_bilstm_is_the_bf16_operand_evaluation(T, B, F, H, monkeypatch):
     """Whose error is the 3e-2 of the comparison with fp32 below?  The rounding of the
     operands to bf16, not the kernels: against the bf16-operand evaluation above the outputs
     agree to 2e-3 of their range (15 times closer than to the fp32 model), and that
-    evaluation itself sits as far from fp32 as the kernels do."""
+    evaluation itself sits as far from fp32 as the kernels do.  The arithmetic of every single
+    step, forward and backward, is pinned per element against an fp64 referee in
+    tests/test_recurrence_referee_gpu.py; this test keeps the free-running view of it."""
     from att_speech.modules.encoders.native_lstm import bilstm
     monkeypatch.setenv('ASR_GX_FP32', '1')          # (paths that run x.W_ih as a GEMM keep it in fp32)
     torch.manual_seed(T * 77 + B)
