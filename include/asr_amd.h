@@ -802,6 +802,54 @@ int asr_edit_distance_stats_i32(const int32_t *x, const int32_t *x_off, const in
                                 const int32_t *y_off, int n_pairs, int max_x, int max_y,
                                 int32_t *out, void *stream);
 
+/*
+ * Forward-backward / alpha scan over ONE weighted sparse graph shared by the batch, in CSR
+ * form (csrc/lattice_shared.hip): the decoding graph HC o G the reference builds when a
+ * grammar FST is given (get_decoding_fst, fst_utils.py:633-640) — the denominator of the
+ * globally normalised loss (advanced_decoder.py:497-505) and the search graph of
+ * FSTDecoder.decode (:536-593).  Same results as asr_lattice_fwbw_f32 /
+ * asr_lattice_forward_f32 (PathLogSumExp.forward fst_utils.py:400-488; path_reduction's alpha
+ * scan :349-397 with the viterbi branch :366-370) on the padded [1,N,K] matrices of the same
+ * graph, up to fp32 summation order; the start state is 0.  These entry points are additions:
+ * no existing signature changes, so the ABI version stays 24.
+ *
+ *   N, E                  states and arcs (epsilon-free; parallel arcs already merged)
+ *   in_ptr  [N+1] i32     in-arcs of state n are in_arc[in_ptr[n] .. in_ptr[n+1]), sorted by
+ *                         (source, ilabel, weight) like the rows of fst_to_matrices (:285)
+ *   in_arc  [E,2] u32     word 0 = source state | ilabel << 16, word 1 = the f32 weight's bits
+ *   out_ptr / out_arc     the same arcs by source state, word 0 = destination | ilabel << 16
+ *   term    [N]   f32     terminal log-weights (neg_inf where not final)
+ *   order_in  [N] i32     the states in the order the scan takes them: the first n_light_in are
+ *                         reduced by lanes_in (1..64, a power of two) adjacent lanes each, the
+ *                         rest (high in-degree) by a whole wave each.  order_out / n_light_out
+ *                         / lanes_out: the same for the beta scan over the out-arcs.
+ *   grad_sign   +1, or -1 for the occupancies of -logZ (as asr_lattice_fwbw_signed_f32)
+ *   accumulate  != 0: out_grad += occupancies, rows past an utterance's end left as they are
+ *               (as asr_lattice_grouped_fwbw_acc_f32)
+ *   out_best_il ties pick the first maximum in in-arc order; rows t >= lens[b] are 0
+ *   workspace: asr_lattice_shared_workspace_bytes(T,B,N) bytes (fwbw always; forward only with
+ *              viterbi != 0 and out_best_il != NULL)
+ * lens[b] == 0 gives logZ = term[0] and an all-zero gradient.  The caller guarantees every
+ * state index < N, every ilabel < C and every in-degree <= 65535.
+ * asr_lattice_shared_supported: N <= 7168 and C <= 1024 (alpha/beta and the rows of a frame
+ * live in 64 KiB of LDS; one log-prob per thread is prefetched); otherwise ASR_EUNSUPPORTED
+ * and the caller runs asr_lattice_fwbw_f32 on the padded matrices.
+ */
+int asr_lattice_shared_supported(int N, int E, int C);
+int64_t asr_lattice_shared_workspace_bytes(int T, int B, int N);
+int asr_lattice_shared_fwbw_f32(
+    const float *lp, int T, int B, int C, const int32_t *lens, int N, int E,
+    const int32_t *in_ptr, const uint32_t *in_arc, const int32_t *out_ptr, const uint32_t *out_arc,
+    const float *term, const int32_t *order_in, int n_light_in, int lanes_in,
+    const int32_t *order_out, int n_light_out, int lanes_out, float neg_inf, float grad_sign,
+    int accumulate, float *out_logZ, float *out_grad, float *out_logZ_bwd, void *workspace,
+    int64_t workspace_bytes, void *stream);
+int asr_lattice_shared_forward_f32(
+    const float *lp, int T, int B, int C, const int32_t *lens, int N, int E,
+    const int32_t *in_ptr, const uint32_t *in_arc, const float *term, const int32_t *order_in,
+    int n_light_in, int lanes_in, float neg_inf, int viterbi, float *out_score,
+    int32_t *out_best_il, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,12 @@ _SIGNATURES = {
                                          [_f, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     'asr_lattice_grouped_forward_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i] + [_vp] * 8 +
                                         [_f, _i, _vp, _vp, _vp, _i64, _vp]),
+    'asr_lattice_shared_supported': (_i, [_i, _i, _i]),
+    'asr_lattice_shared_workspace_bytes': (_i64, [_i, _i, _i]),
+    'asr_lattice_shared_fwbw_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i] + [_vp] * 6 + [_i, _i, _vp, _i, _i,
+                                         _f, _f, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'asr_lattice_shared_forward_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i] + [_vp] * 4 +
+                                       [_i, _i, _f, _i, _vp, _vp, _vp, _i64, _vp]),
     'asr_lstm_workspace_bytes': (_i64, [_i, _i]),
     'asr_lstm_bidir_fwd_bf16': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     'asr_lstm_bidir_bwd_bf16': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
@@ -205,7 +211,7 @@ class Graph(object):
     """Device-resident int32/f32 copy of the reference's 4 or 8 padded graph
     matrices (fst_utils.py:222-294,491-521)."""
     __slots__ = ('src_in', 'il_in', 'w_in', 'term', 'dst_out', 'il_out',
-                 'w_out', 'Bg', 'N', 'Kin', 'Kout', 'band', 'ctc_labels')
+                 'w_out', 'Bg', 'N', 'Kin', 'Kout', 'band', 'ctc_labels', 'addend')
 
     def __init__(self, graph_matrices, device):
         # band: every state n is entered only from {n, n-1, n-2} with weights <= 0 (the CTC
@@ -214,6 +220,10 @@ class Graph(object):
         # (the data workers' hand-over, fst_utils.py:491-521); the kernel re-checks per utterance.
         self.band = False
         self.ctc_labels = None      # (labels [B,Lmax] i32, lens [B] i32) when built from them (order 1)
+        # [B] f32 added to every path sum of utterance b, or None: log G(y) of a grammar FST, which
+        # weights all alignments of a transcript alike (fst_utils.BaseGraphGen), so the chain lattices
+        # stay unweighted and band-shaped
+        self.addend = None
         if graph_matrices is None:          # filled in by build_ctc_graph
             return
         gm = list(graph_matrices)
@@ -367,6 +377,10 @@ def lattice_fwbw(lp, lens, graph, neg_inf=-1e20, want_bwd_total=False, grad_sign
         hook.append((ev0, ev1))
     if use_band and band_env != '2':
         _band_policy_record(lp.device, B)
+    if graph.addend is not None:
+        logZ += graph.addend
+        if zb is not None:
+            zb += graph.addend
     if use_band and os.environ.get('ASR_LATTICE_BAND_DEBUG'):
         # development aid: why utterances were redone by the in-kernel log-domain body (the last
         # word of each utterance's workspace region, csrc/lattice_band.inc); synchronises
@@ -397,6 +411,8 @@ def lattice_forward(lp, lens, graph, neg_inf=-1e20, viterbi=False, want_path=Fal
         _p(graph.w_in), _p(graph.term), graph.N, graph.Kin, graph.Bg,
         float(neg_inf), int(bool(viterbi)), _p(score), _p(best), _p(ws), nbytes,
         _stream()), 'asr_lattice_forward_f32')
+    if graph.addend is not None:
+        score += graph.addend
     return score, best
 
 
@@ -784,6 +800,99 @@ def grouped_forward(lp, lens, gg, neg_inf=-1e20, viterbi=False, want_path=False)
     check(L.asr_lattice_grouped_forward_f32(
         _p(lp), T, B, C, _p(lens), *gg._args(), float(neg_inf), int(bool(viterbi)), _p(score),
         _p(best), _p(ws), nbytes, _stream()), 'asr_lattice_grouped_forward_f32')
+    return score, best
+
+
+class SharedGraph(object):
+    """Device copy of a shared weighted sparse graph in CSR form (include/asr_amd.h,
+    asr_lattice_shared_*), from the bundle fst_utils.shared_structure makes: in_ptr / out_ptr
+    [N+1], in_nb / in_il / in_w and out_nb / out_il / out_w [E] (neighbour state, input label,
+    weight), term [N].  The degree-ordered state lists and the lanes per state are worked out
+    here."""
+    HEAVY = 128          # arcs from which a state gets a whole wave
+
+    def __init__(self, st, device):
+        import numpy as np
+        self.N, self.E = int(len(st['term'])), int(len(st['in_w']))
+        self.C_min = int(max(st['in_il'].max(), 0)) + 1 if self.E else 1
+        if self.N > 65535 or self.C_min > 65536:
+            raise NotImplementedError('shared graph: 16-bit state / label indices')
+
+        def i32(a):
+            return torch.as_tensor(np.ascontiguousarray(a)).to(device=device, dtype=torch.int32).contiguous()
+
+        def arcs(nb, il, w):
+            rec = np.empty((self.E, 2), np.uint32)
+            rec[:, 0] = np.asarray(nb, np.uint32) | (np.asarray(il, np.uint32) << np.uint32(16))
+            rec[:, 1] = np.asarray(w, np.float32).view(np.uint32)
+            return torch.from_numpy(rec.view(np.int32)).to(device).contiguous()
+
+        def order(ptr):
+            deg = np.diff(np.asarray(ptr, np.int64))
+            idx = np.argsort(-deg, kind='stable')            # equal work side by side in a wave
+            heavy = deg[idx] > self.HEAVY
+            idx = np.concatenate([idx[~heavy], idx[heavy]])
+            n_light = int((~heavy).sum())
+            mean = float(deg[deg <= self.HEAVY].mean()) if n_light else 1.0
+            lanes = 1
+            while lanes < 64 and lanes * 2 * n_light <= 1024 and lanes * 2 <= max(1.0, mean):
+                lanes *= 2
+            return i32(idx), n_light, lanes, int(deg.max()) if len(deg) else 0
+        self.in_ptr, self.out_ptr = i32(st['in_ptr']), i32(st['out_ptr'])
+        self.in_arc = arcs(st['in_nb'], st['in_il'], st['in_w'])
+        self.out_arc = arcs(st['out_nb'], st['out_il'], st['out_w'])
+        self.term = torch.as_tensor(np.asarray(st['term'], np.float32)).to(device).contiguous()
+        self.order_in, self.n_light_in, self.lanes_in, self.max_in = order(st['in_ptr'])
+        self.order_out, self.n_light_out, self.lanes_out, _ = order(st['out_ptr'])
+
+    def supported(self, C):
+        return bool(self.E > 0 and self.max_in <= 65535 and C >= self.C_min and
+                    lib().asr_lattice_shared_supported(self.N, self.E, int(C)))
+
+
+def shared_fwbw(lp, lens, sg, neg_inf=-1e20, want_bwd_total=False, add_to=None, grad_sign=1.0):
+    """asr_lattice_shared_fwbw_f32 -> (logZ [B], grad [T,B,C], logZ_bwd | None); add_to: a
+    [T,B,C] f32 tensor the occupancies (times grad_sign) are ADDED to and which is returned as
+    grad."""
+    lp = _dev(lp, torch.float32, 'log_probs')
+    lens = _dev(lens, torch.int32, 'act_lens')
+    T, B, C = lp.shape
+    if C < sg.C_min:
+        raise AssertionError('graph consumes label %d, log_probs have %d classes' % (sg.C_min - 1, C))
+    L = lib()
+    logZ = torch.empty(B, dtype=torch.float32, device=lp.device)
+    if add_to is not None:
+        assert add_to.shape == lp.shape and add_to.is_contiguous() and add_to.dtype == torch.float32
+    grad = torch.empty_like(lp) if add_to is None else add_to
+    zb = torch.empty(B, dtype=torch.float32, device=lp.device) if want_bwd_total else None
+    nbytes = L.asr_lattice_shared_workspace_bytes(T, B, sg.N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=lp.device)
+    check(L.asr_lattice_shared_fwbw_f32(
+        _p(lp), T, B, C, _p(lens), sg.N, sg.E, _p(sg.in_ptr), _p(sg.in_arc), _p(sg.out_ptr),
+        _p(sg.out_arc), _p(sg.term), _p(sg.order_in), sg.n_light_in, sg.lanes_in, _p(sg.order_out),
+        sg.n_light_out, sg.lanes_out, float(neg_inf), float(grad_sign), int(add_to is not None),
+        _p(logZ), _p(grad), _p(zb), _p(ws), nbytes, _stream()), 'asr_lattice_shared_fwbw_f32')
+    return logZ, grad, zb
+
+
+def shared_forward(lp, lens, sg, neg_inf=-1e20, viterbi=False, want_path=False):
+    """asr_lattice_shared_forward_f32 -> (score [B], best_il [T,B] | None)."""
+    lp = _dev(lp, torch.float32, 'log_probs')
+    lens = _dev(lens, torch.int32, 'act_lens')
+    T, B, C = lp.shape
+    if C < sg.C_min:
+        raise AssertionError('graph consumes label %d, log_probs have %d classes' % (sg.C_min - 1, C))
+    L = lib()
+    score = torch.empty(B, dtype=torch.float32, device=lp.device)
+    best, ws, nbytes = None, None, 0
+    if viterbi and want_path:
+        best = torch.empty((T, B), dtype=torch.int32, device=lp.device)
+        nbytes = L.asr_lattice_shared_workspace_bytes(T, B, sg.N)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=lp.device)
+    check(L.asr_lattice_shared_forward_f32(
+        _p(lp), T, B, C, _p(lens), sg.N, sg.E, _p(sg.in_ptr), _p(sg.in_arc), _p(sg.term),
+        _p(sg.order_in), sg.n_light_in, sg.lanes_in, float(neg_inf), int(bool(viterbi)), _p(score),
+        _p(best), _p(ws), nbytes, _stream()), 'asr_lattice_shared_forward_f32')
     return score, best
 
 

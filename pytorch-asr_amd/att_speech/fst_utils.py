@@ -17,6 +17,9 @@ What is different by design:
 """
 from __future__ import absolute_import, division, print_function
 
+import os
+import warnings
+
 import numpy as np
 import torch
 
@@ -98,15 +101,33 @@ class GraphMatrices(list):
     """The reference's list of 4 / 8 padded graph tensors, optionally carrying
     the group-factored description of the same graph (`grouped`, see
     DecodingTransducer.grouped_structure) so that path_reduction can use the
-    closed-form kernels; slicing keeps the tag."""
+    closed-form kernels, or the CSR description of a weighted shared graph (`shared`, see
+    shared_structure) for the asr_lattice_shared_* kernels; slicing keeps the tags."""
     grouped = None
+    shared = None
 
     def __getitem__(self, idx):
         out = list.__getitem__(self, idx)
         if isinstance(idx, slice):
             out = GraphMatrices(out)
             out.grouped = self.grouped
+            out.shared = self.shared
         return out
+
+
+def shared_structure(n_states, src, dst, ilabel, weight, final_weight):
+    """CSR bundle of an epsilon-free weighted graph for the shared-graph kernels
+    (include/asr_amd.h, asr_lattice_shared_*): the in-arcs sorted by destination and the
+    out-arcs sorted by source, each list in the (neighbour, ilabel, weight) order of the padded
+    rows (fst_utils.py:285), so `first maximum` means the same arc in both forms."""
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    il, w = np.asarray(ilabel, np.int64), np.asarray(weight, np.float32)
+    out = {'term': np.asarray(final_weight, np.float32).copy()}
+    for tag, own, other in (('in', dst, src), ('out', src, dst)):
+        order = np.lexsort((w, il, other, own))
+        out[tag + '_ptr'] = np.searchsorted(own[order], np.arange(n_states + 1)).astype(np.int64)
+        out[tag + '_nb'], out[tag + '_il'], out[tag + '_w'] = other[order], il[order], w[order]
+    return out
 
 
 # ----------------------------------------------------------------------------
@@ -161,6 +182,33 @@ def _device_grouped(graph_matrices, device):
     return hit[1]
 
 
+_shared_cache = {}
+
+
+def _device_shared(graph_matrices, device, num_classes):
+    """SharedGraph for matrices tagged by a grammar graph generator's get_decoding_matrices when
+    the native shared-graph kernel is to run them, else None (the caller then runs the generic
+    kernel on the padded matrices of the same graph).  ASR_SHARED_NATIVE=0, read per call,
+    switches the native kernel off; a graph it does not support is reported once."""
+    st = getattr(graph_matrices, 'shared', None)
+    if st is None or os.environ.get('ASR_SHARED_NATIVE', '1') == '0':
+        return None
+    key = (id(st), str(device))
+    hit = _shared_cache.get(key)
+    if hit is None or hit[0] is not st:
+        hit = (st, _native.SharedGraph(st, device))
+        _shared_cache[key] = hit
+    sg = hit[1]
+    if not sg.supported(num_classes):
+        if not _native._WARNED.get('shared_unsupported'):
+            _native._WARNED['shared_unsupported'] = True
+            warnings.warn('shared decoding graph with %d states, %d arcs and %d classes is outside '
+                          'what asr_lattice_shared_* is built for: running the generic (much slower) '
+                          'lattice kernel on its padded matrices' % (sg.N, sg.E, num_classes))
+        return None
+    return sg
+
+
 class PathLogSumExp(torch.autograd.Function):
     """Forward-backward in the log semiring; same contract as the reference's
     PathLogSumExp (fst_utils.py:400-488): returns +logZ per utterance, the
@@ -186,6 +234,11 @@ class PathLogSumExp(torch.autograd.Function):
             log_cost, grads, _ = _native.grouped_fwbw(log_probs, lens, grouped, neg_inf)
             if negate:
                 grads.neg_()
+            ctx.grads = grads
+            return -log_cost if negate else log_cost
+        shared = _device_shared(graph_matrices, log_probs.device, log_probs.size(2))
+        if shared is not None:                    # weighted shared graph (HC o G)
+            log_cost, grads, _ = _native.shared_fwbw(log_probs, lens, shared, neg_inf, grad_sign=sign)
             ctx.grads = grads
             return -log_cost if negate else log_cost
         graph = _device_graph(graph_matrices, log_probs.device)
@@ -229,7 +282,10 @@ class NumeratorMinusDenominator(torch.autograd.Function):
         # (the same constants as the two separate reductions: path_reduction evaluates training
         # lattices with NEG_INF and the decoding graph with the caller's neg_inf)
         zn, grads, _ = _native.lattice_fwbw(log_probs, lens, graph, NEG_INF, grad_sign=-1.0)
-        zd, grads, _ = _native.grouped_fwbw(log_probs, lens, grouped, neg_inf, add_to=grads)
+        if isinstance(grouped, _native.SharedGraph):      # HC o G: the weighted shared-graph kernel
+            zd, grads, _ = _native.shared_fwbw(log_probs, lens, grouped, neg_inf, add_to=grads)
+        else:
+            zd, grads, _ = _native.grouped_fwbw(log_probs, lens, grouped, neg_inf, add_to=grads)
         ctx.grads = grads
         ctx.mark_non_differentiable(zn, zd)
         return zd - zn, zn, zd
@@ -254,6 +310,9 @@ class _PathViterbi(torch.autograd.Function):
         if isinstance(graph, _native.GroupedGraph):
             score, best = _native.grouped_forward(log_probs.detach(), lens, graph,
                                                   neg_inf, viterbi=True, want_path=True)
+        elif isinstance(graph, _native.SharedGraph):
+            score, best = _native.shared_forward(log_probs.detach(), lens, graph,
+                                                 neg_inf, viterbi=True, want_path=True)
         else:
             score, best = _native.lattice_forward(log_probs.detach(), lens, graph,
                                                   neg_inf, viterbi=True, want_path=True)
@@ -276,6 +335,8 @@ class _PathViterbi(torch.autograd.Function):
 def viterbi_path(log_probs, act_lens, graph_matrices, neg_inf=NEG_INF):
     """(score [B], best input label per frame [T,B] int32) of the best path."""
     graph = _device_grouped(graph_matrices, log_probs.device)
+    if graph is None:
+        graph = _device_shared(graph_matrices, log_probs.device, log_probs.size(2))
     if graph is None:
         graph = _device_graph(graph_matrices, log_probs.device)
     return _PathViterbi.apply(log_probs, act_lens, graph, neg_inf)
@@ -315,9 +376,15 @@ def path_reduction(log_probs, act_lens, graph_matrices, red_kind='logsumexp',
             grouped = _device_grouped(graph_matrices, log_probs.device)
             if grouped is not None:
                 return _native.grouped_forward(log_probs, lens, grouped, neg_inf)[0]
+            shared = _device_shared(graph_matrices, log_probs.device, log_probs.size(2))
+            if shared is not None:
+                return _native.shared_forward(log_probs, lens, shared, neg_inf)[0]
             graph = _device_graph(graph_matrices[:4], log_probs.device)
             return _native.lattice_forward(log_probs, lens, graph, neg_inf)[0]
         if getattr(graph_matrices, 'grouped', None) is not None:
+            return path_logsumexp(log_probs, act_lens, graph_matrices, neg_inf)
+        if len(graph_matrices) == 4 and _device_shared(graph_matrices, log_probs.device,
+                                                       log_probs.size(2)) is not None:
             return path_logsumexp(log_probs, act_lens, graph_matrices, neg_inf)
         # differentiable: explicit beta scan needs the out-edge form
         if len(graph_matrices) == 4:
@@ -555,18 +622,229 @@ def ctc_training_arcs(labels, label_lens, num_symbols, context_order,
     return b_, s_, d_, i_, 2 * lens + 1
 
 
+def _segment_push(p, src, dst, ew):
+    """p [B,S] (linear domain) pushed over arcs: returns (unique dst, sum over the arcs into
+    each of p[:, src] * ew)."""
+    order = np.argsort(dst, kind='stable')
+    src, dst, ew = src[order], dst[order], ew[order]
+    starts = np.nonzero(np.r_[True, dst[1:] != dst[:-1]])[0]
+    return dst[starts], np.add.reduceat(p[:, src] * ew[None, :], starts, axis=1)
+
+
+class GrammarGraph(object):
+    """HC o G without OpenFst: the CTC token transducer `hc` (a DecodingTransducer) composed
+    with a grammar acceptor `lm` (an LmFst over the tropical weight set, read as the log
+    semiring like the reference's arcmap(to_log), fst_utils.py:619: scan weights are -arc.weight,
+    terminal weights -final, as fst_to_matrices :263,271).
+
+    The product is taken over arrays: an HC arc whose output label o is not epsilon joins the G
+    arcs with ilabel == o; HC arcs with an epsilon output keep the G state; G's epsilon
+    (back-off) arcs move G alone.  The epsilon arcs are removed by their log-semiring closure
+    (a joint move lands in every state G reaches over epsilons behind it), parallel arcs are
+    merged by logaddexp, and the result is trimmed to the states that are accessible and
+    co-accessible, with the start state numbered 0.
+
+    The reference runs determinize + rmepsilon on the same product (:636-637).  Its state
+    numbering is NOT reproduced: what is pinned is the weighted language, i.e. every path sum
+    and every best path over the input labels.
+
+    `glabel[k]`: the network symbol of G's label k (0 = epsilon, -1 = never matched)."""
+
+    def __init__(self, hc, lm, glabel, nc_weight=NEG_INF):
+        self.hc, self.lm, self.nc_weight = hc, lm, nc_weight
+        Sg = lm.num_states()
+        rank = lm.eps_rank()
+        if rank is None:
+            raise ValueError("grammar FST has epsilon cycles")
+        gl = np.asarray(glabel, np.int64)[lm.ilabel]
+        gl[lm.ilabel == 0] = 0
+        gw = -lm.weight
+        self._gl = gl
+        # log-semiring closure of G's epsilon arcs, [Sg,Sg]: arcs taken in the rank order of their
+        # source, so everything that enters a state is summed before it is pushed on
+        eps = np.nonzero(gl == 0)[0]
+        eps = eps[np.argsort(rank[lm.src[eps]], kind='stable')]
+        cl = np.full((Sg, Sg), -np.inf)
+        cl[np.arange(Sg), np.arange(Sg)] = 0.0
+        for a in eps:
+            s_, d_ = lm.src[a], lm.dst[a]
+            cl[:, d_] = np.logaddexp(cl[:, d_], cl[:, s_] + gw[a])
+        self._eps_arcs = eps
+        gfin = np.where(np.isfinite(lm.final_w), -lm.final_w, -np.inf)
+        c_from, c_to = np.nonzero(np.isfinite(cl))       # sorted by c_from
+        c_w = cl[c_from, c_to]
+        c_ptr = np.searchsorted(c_from, np.arange(Sg + 1))
+
+        # ---- epsilon-free arcs of the product ----
+        hs, hd, hil, hol = hc.arcs()
+        H = hc.num_states
+        NP, C = H * Sg + 1, int(hil.max()) + 1           # + the start state, see below
+        keep = hol == 0                                  # HC alone: every G state, G stays
+        g_all = np.tile(np.arange(Sg), int(keep.sum()))
+        a_src = [np.repeat(hs[keep], Sg) * Sg + g_all]
+        a_dst = [np.repeat(hd[keep], Sg) * Sg + g_all]
+        a_il = [np.repeat(hil[keep], Sg)]
+        a_w = [np.zeros(len(g_all))]
+        for o in np.unique(hol[hol > 0]):                # joint moves on label o
+            ha = np.nonzero(hol == o)[0]
+            ga = np.nonzero(gl == o)[0]
+            if not len(ga):
+                continue
+            # the G arc followed by the closure of its destination
+            owner, idx = _gather_arcs(c_ptr[:-1][lm.dst[ga]], c_ptr[1:][lm.dst[ga]])
+            g_s, g_d, g_w = lm.src[ga][owner], c_to[idx], gw[ga][owner] + c_w[idx]
+            a_src.append(np.repeat(hs[ha], len(g_s)) * Sg + np.tile(g_s, len(ha)))
+            a_dst.append(np.repeat(hd[ha], len(g_s)) * Sg + np.tile(g_d, len(ha)))
+            a_il.append(np.repeat(hil[ha], len(g_s)))
+            a_w.append(np.tile(g_w, len(ha)))
+        src, dst, il, w = [np.concatenate(x) for x in (a_src, a_dst, a_il, a_w)]
+        fin = np.concatenate([np.tile(gfin, H), [-np.inf]])
+        # G's epsilon arcs are taken right after a move of G and nowhere else: one path per
+        # (alignment, G path), as the epsilon filter of a composition arranges it.  Before the first
+        # move that leaves the closure of G's start state, which a start state of its own carries:
+        # it has the arcs and the final weight of (HC start, g) for every g G reaches at no input
+        start = NP - 1
+        g0 = lm.start()
+        for g, c in zip(c_to[c_ptr[g0]:c_ptr[g0 + 1]], c_w[c_ptr[g0]:c_ptr[g0 + 1]]):
+            m = src == 0 * Sg + g                        # HC starts in state 0
+            src, dst, il, w = (np.concatenate([src, np.full(int(m.sum()), start)]),
+                               np.concatenate([dst, dst[m]]), np.concatenate([il, il[m]]),
+                               np.concatenate([w, w[m] + c]))
+            fin[start] = np.logaddexp(fin[start], c + gfin[g])
+        key = (src * NP + dst) * C + il
+        order = np.argsort(key, kind='stable')
+        key, w = key[order], w[order]
+        first = np.nonzero(np.r_[True, key[1:] != key[:-1]])[0]
+        w = np.logaddexp.reduceat(w, first)              # parallel arcs merged
+        src, dst, il = src[order][first], dst[order][first], il[order][first]
+
+        # ---- trim, start state first ----
+        acc = np.zeros(NP, bool); acc[start] = True
+        while True:
+            nxt = acc.copy(); nxt[dst[acc[src]]] = True
+            if nxt.sum() == acc.sum():
+                break
+            acc = nxt
+        coacc = np.isfinite(fin)
+        while True:
+            nxt = coacc.copy(); nxt[src[coacc[dst]]] = True
+            if nxt.sum() == coacc.sum():
+                break
+            coacc = nxt
+        live = acc & coacc
+        if not live[start]:
+            raise ValueError("HC o G accepts nothing")
+        old = np.concatenate([[start], np.nonzero(live & (np.arange(NP) != start))[0]])
+        new_id = np.full(NP, -1, np.int64); new_id[old] = np.arange(len(old))
+        ok = live[src] & live[dst]
+        self.num_states = len(old)
+        # (HC state, G state) of every state; state 0, the start, is (0, G's start) before any move
+        self.state_pairs = np.stack([old // Sg, old % Sg], 1)
+        self.state_pairs[0] = (0, g0)
+        self.src, self.dst, self.ilabel = new_id[src[ok]], new_id[dst[ok]], il[ok]
+        self.weight = w[ok].astype(np.float32)
+        f = fin[old]
+        self.final = np.where(np.isfinite(f), f, nc_weight).astype(np.float32)
+
+    def log_score_batch(self, labels, label_lens):
+        """log G(y) per transcript: the log-sum over all G paths that accept it, back-off arcs and
+        the final weight included; nc_weight when G does not accept it.  All transcripts advance
+        together, one label position per step, in the linear domain with a per-row scale."""
+        lm, gl = self.lm, self._gl
+        labels = np.asarray(labels, np.int64)
+        lens = np.asarray(label_lens, np.int64)
+        B, Sg = len(lens), lm.num_states()
+        ew = np.exp(-lm.weight)
+        eps = self._eps_arcs
+        rank = lm.eps_rank()
+        levels = [eps[rank[lm.src[eps]] == r] for r in range(int(rank.max()) + 1)] if len(eps) else []
+
+        def close(p):
+            for lv in levels:
+                if len(lv):
+                    d, add = _segment_push(p, lm.src[lv], lm.dst[lv], ew[lv])
+                    p[:, d] += add
+            return p
+        p = np.zeros((B, Sg)); p[:, lm.start()] = 1.0
+        p = close(p)
+        scale = np.zeros(B)
+        by_label = {}
+        for j in range(int(lens.max()) if B else 0):
+            rows = np.nonzero(j < lens)[0]
+            q = np.zeros((len(rows), Sg))
+            lab = labels[rows, j]
+            for o in np.unique(lab):
+                if o not in by_label:
+                    by_label[o] = np.nonzero(gl == o)[0] if o > 0 else np.zeros(0, np.int64)
+                arcs, sel = by_label[o], np.nonzero(lab == o)[0]
+                if len(arcs):
+                    d, add = _segment_push(p[rows[sel]], lm.src[arcs], lm.dst[arcs], ew[arcs])
+                    q[np.ix_(sel, d)] = add
+            q = close(q)
+            top = q.max(1)
+            live = top > 0
+            q[live] /= top[live, None]
+            scale[rows[live]] += np.log(top[live])
+            p[rows] = q
+        tot = (p * np.exp(-lm.final_w)[None, :]).sum(1)
+        with np.errstate(divide='ignore'):
+            out = np.log(tot) + scale
+        return np.where(tot > 0, out, self.nc_weight)
+
+
+def _read_vocabulary(vocabulary):
+    """symbols in network order: a list, or a file with one symbol per line (a line holding one
+    blank is the space symbol, as in the reference's vocabulary files)"""
+    if isinstance(vocabulary, str):
+        with open(vocabulary) as f:
+            vocabulary = [line.rstrip('\n') for line in f]
+        while vocabulary and vocabulary[-1] == '':
+            vocabulary.pop()
+    return list(vocabulary)
+
+
+def grammar_labels(lm, vocabulary, num_symbols):
+    """Network symbol of every label of the grammar FST, matched by NAME under the renaming of the
+    reference's get_grammar_fst (fst_utils.py:615-631: ' ' -> <spc>, <pad> -> <eps>); <s> and </s>
+    match nothing (-1).  A label on an arc of G without a network symbol is a ValueError."""
+    syms = lm.input_symbols()
+    used = np.unique(lm.ilabel)
+    if syms is None:                       # no table: the labels are network symbols already
+        if len(used) and used.max() >= num_symbols:
+            raise ValueError("grammar label %d outside the %d network symbols" % (used.max(), num_symbols))
+        return np.arange(max(int(used.max()) + 1 if len(used) else 1, 1))
+    net = {{' ': '<spc>', '<pad>': '<eps>'}.get(sym, sym): i for i, sym in enumerate(vocabulary)}
+    top = max([k for k, _ in syms] + [int(used.max()) if len(used) else 0])
+    out = np.full(top + 1, -1, np.int64)
+    for k, sym in syms:
+        if sym not in ('<s>', '</s>'):
+            out[k] = net.get(sym, -2)
+    out[0] = 0
+    for k in used:
+        sym = syms.find(int(k))
+        if sym in ('<s>', '</s>'):
+            continue
+        if out[k] < 0 or out[k] >= num_symbols:
+            raise ValueError("grammar symbol %r (label %d) has no network symbol" % (sym, k))
+    out[out < 0] = -1
+    return out
+
+
 class BaseGraphGen(object):
-    """reference fst_utils.py:546-676 (grammar-FST composition excluded: it
-    needs an external LM FST)."""
+    """reference fst_utils.py:546-676.  With `grammar_fst` (an OpenFst binary file, plain or
+    gzip-compressed, or an LmFst) and `vocabulary` (the network symbols, a list or a file) the
+    decoding graph is HC o G (GrammarGraph: the weighted language of the reference's graph, not
+    its state numbering) and every training lattice is weighted by log G(transcript)."""
 
     def __init__(self, num_symbols=None, num_classes=None,
                  ngram_to_class_file=None, context_order=None,
                  nc_weight=NEG_INF, for_forward_only=False,
                  grammar_fst=None, vocabulary=None, **kwargs):
         super(BaseGraphGen, self).__init__(**kwargs)
-        if ngram_to_class_file is not None or grammar_fst is not None:
+        if ngram_to_class_file is not None:
             raise NotImplementedError(
-                "ngram_to_class_file / grammar_fst graphs need OpenFst")
+                "ngram_to_class_file graphs (class tables read from a file) are not built by the "
+                "closed-form generator")
         self.num_classes = num_classes
         self.num_symbols = num_symbols
         self.context_order = context_order
@@ -578,9 +856,13 @@ class BaseGraphGen(object):
         setattr_matched(self, 'num_classes', num_classes)
         self.ngram_to_class = ngram_to_class
         self.ngrams = ngram_to_class.tolist()
-        self.grammar_fst_path = None
+        self.grammar_fst_path = grammar_fst
+        self.vocabulary = _read_vocabulary(vocabulary) if vocabulary is not None else None
         self.nc_weight = nc_weight
+        # decoding_fst stays the HC transducer: it maps input labels to output labels
+        # (read_out), and G, an acceptor, does not change that; `grammar` is HC o G
         self.decoding_fst = self.get_decoding_fst()
+        self.grammar = self.get_grammar_graph() if grammar_fst is not None else None
         self.decoding_mats = {}
         self.for_forward_only = for_forward_only
 
@@ -589,6 +871,21 @@ class BaseGraphGen(object):
 
     def get_hc_fst(self):
         raise NotImplementedError()
+
+    def get_grammar_graph(self):
+        """(:615-640) G read and relabelled to the network symbols, composed with HC."""
+        from att_speech.lm_fst import LmFst
+        lm = self.grammar_fst_path
+        if not isinstance(lm, LmFst):
+            lm = LmFst.read(lm)
+        if self.vocabulary is None and lm.input_symbols() is not None:
+            raise ValueError("grammar_fst with a symbol table needs `vocabulary`")
+        glabel = grammar_labels(lm, self.vocabulary, self.num_symbols)
+        return GrammarGraph(self.decoding_fst, lm, glabel, self.nc_weight)
+
+    def _grammar_scores(self, labels, label_lens):
+        """log G(y) [B] float64 of the (reduced, padded) transcripts"""
+        return self.grammar.log_score_batch(labels, label_lens)
 
     def _reduce_labels(self, labels):                           # (:592-600)
         if isinstance(labels, torch.Tensor):
@@ -629,6 +926,13 @@ class BaseGraphGen(object):
         term[bi, n_states - 1, 0] = 0.0            # blank after the last label
         has = label_lens > 0
         term[bi[has], n_states[has] - 2, 0] = 0.0  # last label state
+        if self.grammar is not None:
+            # compose(HC o G, chain(y)) weights every alignment of y by G(y): the chain lattice
+            # plus one constant per utterance, written into its terminal entries
+            logg = self._grammar_scores(labels, label_lens).astype(np.float32)
+            term = np.where(term > self.nc_weight * 0.5,
+                            np.where(logg > self.nc_weight * 0.5, logg, self.nc_weight)[:, None, None],
+                            term).astype(np.float32)
         mats = self._batched(B, nmax, d_, s_, i_, w_, b_) + [torch.from_numpy(term)]
         if not self.for_forward_only:
             mats += self._batched(B, nmax, s_, d_, i_, w_, b_) + [
@@ -657,9 +961,13 @@ class BaseGraphGen(object):
         d = self.decoding_fst
         lab_d = torch.as_tensor(np.ascontiguousarray(labels)).to(device, torch.int32)
         len_d = torch.as_tensor(label_lens).to(device, torch.int32)
-        return _native.build_ctc_graph(lab_d, len_d, self.num_symbols, self.context_order,
-                                       d.allow_nonblank_selfloops, d.use_contextual_blanks,
-                                       self.nc_weight)
+        graph = _native.build_ctc_graph(lab_d, len_d, self.num_symbols, self.context_order,
+                                        d.allow_nonblank_selfloops, d.use_contextual_blanks,
+                                        self.nc_weight)
+        if self.grammar is not None:       # log G(y) as an addend: the lattices stay band-shaped
+            graph.addend = torch.as_tensor(self._grammar_scores(labels, label_lens),
+                                           dtype=torch.float32).to(device)
+        return graph
 
     def _batched(self, B, nmax, own, other, il, w, b):
         st, ilab, wt = _arcs_to_matrices(B * nmax, b * nmax + own, other, il, w,
@@ -681,6 +989,14 @@ class BaseGraphGen(object):
         if ret is not None:
             return ret
         d = self.decoding_fst
+        if self.grammar is not None:
+            g = self.grammar
+            mats = arcs_to_graph_matrices(g.num_states, g.src, g.dst, g.ilabel, g.weight, g.final,
+                                          self.nc_weight, self.for_forward_only)
+            tagged = GraphMatrices(m.unsqueeze(0).to(device) for m in mats)
+            tagged.shared = shared_structure(g.num_states, g.src, g.dst, g.ilabel, g.weight, g.final)
+            self.decoding_mats[key] = tagged
+            return tagged
         src, dst, il, _ = d.arcs()
         mats = arcs_to_graph_matrices(
             d.num_states, src, dst, il, np.zeros(len(src), np.float32),

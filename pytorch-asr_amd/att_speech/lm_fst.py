@@ -11,10 +11,12 @@ container with that same surface, stored as flat numpy arrays in CSR order
 Readers: the AT&T text format (`fstprint` output: `src dst ilabel olabel
 [weight]`, final states `state [weight]`) with optional symbol-table text files,
 and the OpenFst binary `vector` / `standard` (tropical, float32) file format as
-published in OpenFst's fst.h / vector-fst.h / symbol-table.cc.  PARITY UNPINNED
-for the binary reader: no OpenFst build and no binary FST fixture exists in this
-environment; it is covered by a write -> read round trip only.
+published in OpenFst's fst.h / vector-fst.h / symbol-table.cc.  The binary reader is
+pinned on the reference's shipped character LMs (tests/golden/G_char_*_syms.fst.gz: state,
+arc and epsilon counts, symbol tables, and the path sums of graphs built from them).
 """
+import gzip
+import io
 import struct
 
 import numpy as np
@@ -205,10 +207,24 @@ class LmFst(object):
 
     @classmethod
     def read(cls, path):
-        with open(path, 'rb') as f:
+        """`path`: a file name (OpenFst binary, gzip-compressed binary such as the reference's
+        egs/wsj/train_lm/*.fst.gz, or AT&T text), the bytes of a binary FST, or a binary file
+        object."""
+        if isinstance(path, (bytes, bytearray)):
+            data = bytes(path)
+        elif hasattr(path, 'read'):
+            data = path.read()
+        else:
+            with open(path, 'rb') as f:
+                data = f.read()
+        if data[:2] == b'\x1f\x8b':
+            data = gzip.decompress(data)
+        with io.BytesIO(data) as f:
             head = f.read(4)
             if len(head) < 4 or struct.unpack('<i', head)[0] != _FST_MAGIC:
-                return cls.read_text(path)
+                if isinstance(path, str):
+                    return cls.read_text(path)
+                raise ValueError("not an OpenFst binary FST")
             fsttype, arctype = cls._rd_str(f), cls._rd_str(f)
             if fsttype != 'vector' or arctype != 'standard':
                 raise ValueError("unsupported FST file type %s/%s (vector/standard only)"

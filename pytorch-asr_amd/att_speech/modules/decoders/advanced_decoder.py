@@ -632,6 +632,8 @@ class FSTDecoder(_ProjectionDecoder):
             # both reductions in one autograd node: one gradient buffer, no [T,B,C] addition
             den_graph = gg.get_decoding_matrices('cpu')
             grouped = fst_utils._device_grouped(den_graph, shifted.device)
+            if grouped is None:           # HC o G (graph generator with a grammar_fst)
+                grouped = fst_utils._device_shared(den_graph, shifted.device, shifted.size(2))
             num_ok = isinstance(numerator, _native.Graph) or len(numerator) == 8
             if grouped is not None and num_ok:
                 return fst_utils.NumeratorMinusDenominator.apply(
