@@ -552,6 +552,7 @@ int asr_conv1c_7x7s2_wgrad(const float *x, const void *dy, int B, int T, int F, 
  *           null): hypothesis h continues row parent[h] (the beam's re-indexing, :551)
  *   att_new [B*beam, T]  softmax_t( w . tanh(eproj_t + (a_prev * filt)(t) + glob) * temperature + pad_t )
  *   context [B*beam, E]  sum_t att_new[t] enc[t]
+ * Limits: Kf == 32, T <= 8160 (two alignment rows in 64 KiB of LDS; ASR_EUNSUPPORTED beyond).
  */
 int asr_tcn_attention_step_f32(const float *eproj, const float *enc, const int32_t *enc_lens,
                                const float *filt, const float *glob, const float *w_score,
@@ -661,7 +662,13 @@ int asr_att_gru_scan_bwd_f32(const float *eproj, const float *encoded, const int
  * change nothing, so a host polling it every few steps sees the reference's results; word 2
  * counts the steps that took effect (the final histories are in the buffer written by the
  * last of them), word 1 is scratch.
- * Ties in the top-k go to the lower candidate index.  beam <= 32, beam * (C-1) <= 2048.
+ * Ties: the top-k is a stable descending sort of the candidates beam * (C-1) + class, so equal
+ * scores go to the lower candidate index, -inf ones included (they fill the slots the finite
+ * candidates leave; with fewer candidates than beams the rest are -inf copies of the last sorted
+ * index); EOS must be strictly above every other class of its row to count as best, and a row
+ * whose running score is -inf never does; among beams with equal normalised EOS scores the first
+ * wins; a best_score equal to the candidate stays.  beam <= 32, beam * (C-1) <= 2048
+ * (ASR_EUNSUPPORTED beyond); Lcap > step (ASR_EINVAL).
  */
 int asr_beam_step_f32(const float *logits, const float *scores_in, float *scores_out,
                       const int32_t *est_in, int32_t *est_out, int step, int B, int beam, int C,

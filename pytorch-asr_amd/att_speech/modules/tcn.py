@@ -224,6 +224,7 @@ class LocalAttention(nn.Module):
 
 _SCAN_MAX_FRAMES = 4096     # asr_tcn_attention_scan_*_f32: longest encoder sequence
 _SCAN_MAX_WIDTH = 256       # ... and widest attention
+_STEP_MAX_FRAMES = 8160     # asr_tcn_attention_step_f32: two alignment rows in 64 KiB of LDS
 
 
 class _AttentionScan(torch.autograd.Function):
@@ -452,7 +453,7 @@ class AttentionDecoderTCN(nn.Module):
             return False
         return (encoded.is_cuda and not self.lm and not self.training
                 and not self.attn.force_forward and self.attn.kernel_size == 32
-                and beam <= 32 and beam * (C - 1) <= 2048 and encoded.dtype == torch.float32)
+                and 1 <= encoded.size(0) <= _STEP_MAX_FRAMES and beam <= 32 and beam * (C - 1) <= 2048 and encoded.dtype == torch.float32)
 
     def _decode_native(self, encoded, encoded_lens, return_attention, poll_every=8):
         """The MI355X decode loop for the plain beam search: per label step the LM state of

@@ -165,7 +165,9 @@ __global__ __launch_bounds__(BEAM_NT) void beam_step_kernel(BeamParams p) {
         float mo = -INFINITY;
         for (int c = lane; c < Cm; c += 64) mo = fmaxf(mo, qrow[c]);
         mo = wave_max(mo);
-        const bool eos_best = qrow[Cm] > mo;           // argmax == C-1: first maximum wins
+        // argmax == C-1, the first maximum wins a tie; a dead hypothesis (running score -inf) has
+        // -inf in every class, so its argmax is class 0
+        const bool eos_best = qrow[Cm] > mo && p.scores_in[b] > -INFINITY;
         // best length-normalised EOS score among the utterance's beams (first maximum)
         const float ln = p.len_div;      // step ** length_normalization, computed by the host
         float bestn = -INFINITY, bestr = 0.f;
@@ -200,7 +202,9 @@ __global__ __launch_bounds__(BEAM_NT) void beam_step_kernel(BeamParams p) {
 #pragma unroll
         for (int i = 0; i < CAND_PER_THREAD; ++i) {
             const int idx = tid + i * BEAM_NT;
-            if (idx < ncand && (cv[i] > bv || (cv[i] == bv && idx < bidx)) && cv[i] > -INFINITY) {
+            // (-inf candidates are taken too, in index order, once the finite ones are gone;
+            // a taken candidate is NaN and compares false)
+            if (idx < ncand && (cv[i] > bv || (cv[i] == bv && idx < bidx))) {
                 bv = cv[i];
                 bidx = idx;
             }
@@ -223,9 +227,10 @@ __global__ __launch_bounds__(BEAM_NT) void beam_step_kernel(BeamParams p) {
         const int win = sel_i[r];
 #pragma unroll
         for (int i = 0; i < CAND_PER_THREAD; ++i)
-            if (tid + i * BEAM_NT == win) cv[i] = -INFINITY;      // taken
+            if (tid + i * BEAM_NT == win) cv[i] = NAN;            // taken
     }
-    // fewer candidates than beams (:86-97): -inf scores, the last index repeated
+    // fewer candidates than beams (:86-97): -inf scores, the last index of the sorted
+    // candidates repeated
     if (tid == 0) {
         int last = 0;
         for (int r = 0; r < beam; ++r) {
