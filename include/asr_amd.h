@@ -677,6 +677,82 @@ int asr_beam_step_f32(const float *logits, const float *scores_in, float *scores
                       int32_t *parent, int32_t *done_and_scratch, void *stream);
 
 /*
+ * The LM-fused beam search (BeamSearchLM, reference att_speech/modules/beam_search.py:185-363) on
+ * the device, for any number of utterances; additions to ABI v24.  A batch of B utterances behaves
+ * as B independent BeamSearchLM(batch_size = 1) runs, each on its own enc_lens[b] frames.
+ *
+ * The LM is the CSR bundle of att_speech.lm_fst.LmFst: ptr [S+1] (arcs of s are [ptr[s], ptr[s+1]),
+ * ilabel-sorted, so its epsilon arcs are [ptr[s], ptr_ne[s])), dst / ilabel [A] int32, weight [A]
+ * fp64 (costs, -log p), rank [S] = eps_rank() (every epsilon arc climbs in rank; max_rank its
+ * maximum), and arc_w_closed [A] = weight[a] - log Z(dst[a]) with Z(n) the total weight of all
+ * epsilon paths out of n, the empty one included.  mapping [C]: LM label of every class.
+ * A hypothesis carries a bag of at most ASR_LM_BAG_CAP entries: bag_state [hyps, cap] int32 in
+ * ascending state order, bag_cost [hyps, cap] fp64, bag_n [hyps]; bag_cap must be ASR_LM_BAG_CAP
+ * (ASR_EUNSUPPORTED otherwise).
+ *
+ * asr_lm_label_costs_f64: cost [hyps, C] fp64, cost[h, c] = -log sum over the entries (s, w) of
+ * bag h and the arcs a of s with ilabel mapping[c] of exp(-(w + arc_w_closed[a])), +inf where there
+ * is no such arc: the cost of the epsilon-closed bag of the extension, without building it.
+ * Summed in the order (entry, arc).  frozen [B] (may be NULL): rows of utterances with frozen[b] != 0
+ * are left alone.
+ *
+ * asr_beam_lm_step_f32: one BeamSearchLM.step per utterance, one workgroup each, no read-back.
+ * logits [hyps, C] (class C-1 = EOS), att [hyps, T] this step's alignment, lm_cost as above (NULL:
+ * no LM term, lm_weight == 0).  total = acoustic + (float)(-lm_weight * min(1e20, lm_cost))
+ * (+ coverage_weight * #{t < len : cov_in + att > coverage_tau} when coverage_weight > 0); only the
+ * acoustic part is carried in scores_in / scores_out [hyps].  min_eos [hyps] (NULL: keep_eos_score
+ * off; init -inf): the EOS logit is raised to it before the log-softmax and it is re-indexed in
+ * place.  est_in / est_out [hyps, Lcap], cov_in / cov_out [hyps, T] (init 0; may be NULL when
+ * coverage_weight <= 0) are distinct buffers that the caller alternates.  From step 1 on a
+ * hypothesis finishes when EOS is strictly the best class of its total row, the peak of its
+ * alignment (first maximum over t < len) is > min_attention_pos * len, and total[EOS] / len_div is
+ * > -1e10.  The finished list is double-buffered by fin_parity [B] (0 / 1, flipped by a step that
+ * adds): fin_score / fin_len / fin_beam [2, B, beam], fin_tokens [2, B, beam, Lcap], fin_count [B];
+ * sorted descending and stable (older entries first), cut to beam.  In a step that added, on a
+ * strict improvement over best_score [B] (init -inf): best_len, best_tokens [B, Lcap] and
+ * best_elems [B, 3] = {acoustic, lm, coverage} of THIS step's EOS column at the beam index stored
+ * with entry 0 (the reference's quirk; the third element is left alone when coverage_weight <= 0).  The top-k runs on total over beam * (C-1) + class
+ * (first step: beam 0 only; lowest index wins ties; -inf candidates fill up in index order; with
+ * fewer candidates than beams the last sorted index is repeated), slots r >= ncand get score -inf,
+ * and when beam == ncand EVERY slot does (the reference's slice `[-0:]`).  Outputs new_input /
+ * parent [hyps].  nsteps [B] = step + 1 for every utterance the launch worked on; frozen [B]
+ * (init 0) is set after the step that filled the finished list, and launches change nothing of a
+ * frozen utterance.  Limits as asr_beam_step_f32: beam <= 32, beam * (C-1) <= 2048.
+ *
+ * asr_lm_bag_advance_f64: the bags of the survivors of that step (utterances with nsteps[b] ==
+ * step + 1): from the bag of parent[h], the arcs with ilabel mapping[new_input[h]] (plain weight),
+ * equal targets merged, closed over the epsilon arcs level by level in rank order.  in_* and out_*
+ * are distinct buffers.  A bag that asks for more than bag_cap entries is cut and raises
+ * *overflow (int32, init 0) to the size it asked for (an integer max; a lower bound once entries
+ * are dropped): the caller discards the search.
+ *
+ * Every sum has a fixed owner and order: launches are reproducible bit for bit.
+ */
+#define ASR_LM_BAG_CAP 32
+int asr_beam_lm_supported(int beam, int C, int bag_cap);
+int asr_lm_label_costs_f64(const int32_t *ptr, const int32_t *ilabel, const double *arc_w_closed,
+                           int nstates, const int32_t *bag_state, const double *bag_cost,
+                           const int32_t *bag_n, int bag_cap, const int32_t *mapping,
+                           const int32_t *frozen, int B, int beam, int C, double *cost, void *stream);
+int asr_lm_bag_advance_f64(const int32_t *ptr, const int32_t *ptr_ne, const int32_t *dst,
+                           const int32_t *ilabel, const double *weight, const int32_t *rank,
+                           int nstates, int max_rank, const int32_t *mapping,
+                           const int32_t *in_state, const double *in_cost, const int32_t *in_n,
+                           int32_t *out_state, double *out_cost, int32_t *out_n, int bag_cap,
+                           const int32_t *parent, const int32_t *new_input, const int32_t *nsteps,
+                           int step, int B, int beam, int32_t *overflow, void *stream);
+int asr_beam_lm_step_f32(const float *logits, const float *att, const int32_t *enc_lens,
+                         const double *lm_cost, double lm_weight, const float *scores_in,
+                         float *scores_out, const int32_t *est_in, int32_t *est_out,
+                         const float *cov_in, float *cov_out, float *min_eos, int step, int B,
+                         int beam, int C, int T, int Lcap, float len_div, double min_attention_pos,
+                         float coverage_tau, float coverage_weight, int32_t *fin_count,
+                         int32_t *fin_parity, float *fin_score, int32_t *fin_len, int32_t *fin_beam,
+                         int32_t *fin_tokens, float *best_score, int32_t *best_len,
+                         int32_t *best_tokens, float *best_elems, int32_t *new_input,
+                         int32_t *parent, int32_t *frozen, int32_t *nsteps, void *stream);
+
+/*
  * The step boundary on the device (ABI v18): the reference's GradientClipping hook
  * (att_speech/modules/hooks/gradient_clipping.py:13-53: clip_grad_norm_ to clip_norm, skip the
  * optimizer step when the unclipped norm exceeds skip_step_norm) and torch.optim.Adam.step

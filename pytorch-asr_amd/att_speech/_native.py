@@ -86,6 +86,11 @@ _SIGNATURES = {
     'asr_att_gru_scan_bwd_f32': (_i, [_vp] * 14 + [_i] * 6 + [_vp] * 7),
     'asr_beam_step_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'asr_beam_lm_supported': (_i, [_i, _i, _i]),
+    'asr_lm_label_costs_f64': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'asr_lm_bag_advance_f64': (_i, [_vp] * 6 + [_i, _i] + [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'asr_beam_lm_step_f32': (_i, [_vp, _vp, _vp, _vp, ctypes.c_double] + [_vp] * 7 + [_i] * 6 +
+                             [_f, ctypes.c_double, _f, _f] + [_vp] * 15),
     'asr_ctc_graph_build': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f] + [_vp] * 8),
     'asr_lattice_grouped_workspace_bytes': (_i64, [_i, _i, _i, _i]),
     'asr_lattice_grouped_fwbw_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i] + [_vp] * 8 +
@@ -1163,6 +1168,49 @@ def att_gru_scan_bwd(eproj, encoded, enc_lens, w_icT, w_hhT, w_recT, w_score, h0
         _p(d_eproj), _p(d_gates), _p(d_ctx), _p(d_rec), _p(d_v), _p(d_h0), _stream()),
         'asr_att_gru_scan_bwd_f32')
     return d_eproj, d_gates, d_ctx, d_rec, d_v, d_h0
+
+
+LM_BAG_CAP = 32
+
+
+def beam_lm_supported(beam, C, bag_cap=LM_BAG_CAP):
+    return bool(lib().asr_beam_lm_supported(beam, C, bag_cap))
+
+
+def lm_label_costs(lm, bag_state, bag_cost, bag_n, mapping, frozen, B, beam, C, cost, bag_cap=LM_BAG_CAP):
+    """asr_lm_label_costs_f64: `lm` = LmFst.device_arrays(); writes cost [B*beam, C] fp64."""
+    check(lib().asr_lm_label_costs_f64(
+        _p(lm['ptr']), _p(lm['ilabel']), _p(lm['w_closed']), lm['nstates'], _p(bag_state), _p(bag_cost),
+        _p(bag_n), bag_cap, _p(mapping), _p(frozen), B, beam, C, _p(cost), _stream()),
+        'asr_lm_label_costs_f64')
+    return cost
+
+
+def lm_bag_advance(lm, mapping, bags_in, bags_out, parent, new_input, nsteps, step, B, beam, overflow,
+                   bag_cap=LM_BAG_CAP):
+    """asr_lm_bag_advance_f64: bags_* = (state [hyps, cap] i32, cost [hyps, cap] f64, n [hyps] i32)."""
+    check(lib().asr_lm_bag_advance_f64(
+        _p(lm['ptr']), _p(lm['ptr_ne']), _p(lm['dst']), _p(lm['ilabel']), _p(lm['weight']), _p(lm['rank']),
+        lm['nstates'], lm['max_rank'], _p(mapping), _p(bags_in[0]), _p(bags_in[1]), _p(bags_in[2]),
+        _p(bags_out[0]), _p(bags_out[1]), _p(bags_out[2]), bag_cap, _p(parent), _p(new_input),
+        _p(nsteps), step, B, beam, _p(overflow), _stream()), 'asr_lm_bag_advance_f64')
+
+
+def beam_lm_step(logits, att, lens, lm_cost, lm_weight, scores_in, scores_out, est_in, est_out, cov_in,
+                 cov_out, min_eos, step, B, beam, len_div, min_attention_pos, coverage_tau,
+                 coverage_weight, state):
+    """asr_beam_lm_step_f32; `state` = dict of the per-utterance device arrays (fin_count, fin_parity,
+    fin_score, fin_len, fin_beam, fin_tokens, best_score, best_len, best_tokens, best_elems,
+    new_input, parent, frozen, nsteps)."""
+    C, T = logits.shape[-1], att.shape[-1]
+    check(lib().asr_beam_lm_step_f32(
+        _p(logits), _p(att), _p(lens), _p(lm_cost), float(lm_weight), _p(scores_in), _p(scores_out),
+        _p(est_in), _p(est_out), _p(cov_in), _p(cov_out), _p(min_eos), step, B, beam, C, T,
+        est_in.shape[1], len_div, float(min_attention_pos), coverage_tau, coverage_weight,
+        _p(state['fin_count']), _p(state['fin_parity']), _p(state['fin_score']), _p(state['fin_len']),
+        _p(state['fin_beam']), _p(state['fin_tokens']), _p(state['best_score']), _p(state['best_len']),
+        _p(state['best_tokens']), _p(state['best_elems']), _p(state['new_input']), _p(state['parent']),
+        _p(state['frozen']), _p(state['nsteps']), _stream()), 'asr_beam_lm_step_f32')
 
 
 def beam_step(logits, scores_in, scores_out, est_in, est_out, step, B, beam, len_div, state):

@@ -143,6 +143,62 @@ class LmFst(object):
             self._eps_rank = rank if seen == self._n else None
         return self._eps_rank
 
+    def log_eps_z(self):
+        """log Z(n) per state: the log of the total weight of all epsilon paths out of n, the empty
+        one included.  The epsilon closure is linear in the log semiring, so the cost of a closed
+        bag is the cost of the open one with every state n weighted by Z(n).  Computed walking the
+        eps_rank() levels backwards (a state's successors over epsilon arcs have a higher rank);
+        None when the epsilon graph has a cycle."""
+        rank = self.eps_rank()
+        if rank is None:
+            return None
+        logz = np.zeros(self._n)
+        eps = np.nonzero(self.ilabel == 0)[0]
+        if len(eps):
+            r = rank[self.src[eps]]
+            for level in range(int(r.max()), -1, -1):
+                a = eps[r == level]
+                if len(a):
+                    np.logaddexp.at(logz, self.src[a], logz[self.dst[a]] - self.weight[a])
+        return logz
+
+    def __getstate__(self):
+        """the device copies stay out of pickles and deep copies (rebuilt on demand)"""
+        state = dict(self.__dict__)
+        state.pop('_device_arrays', None)
+        return state
+
+    def arc_w_closed(self):
+        """weight[a] - log Z(dst[a]): an arc followed by every epsilon path behind it."""
+        if getattr(self, '_arc_w_closed', None) is None:
+            logz = self.log_eps_z()
+            self._arc_w_closed = None if logz is None else self.weight - logz[self.dst]
+        return self._arc_w_closed
+
+    def device_arrays(self, device):
+        """The CSR bundle of include/asr_amd.h (asr_lm_label_costs_f64 / asr_lm_bag_advance_f64) as
+        tensors on `device`, built once per device; None when the epsilon graph has a cycle."""
+        import torch
+        cache = self.__dict__.setdefault('_device_arrays', {})
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:          # 'cuda' and 'cuda:0': one copy
+            device = torch.device('cuda', torch.cuda.current_device())
+        key = device
+        if key not in cache:
+            wc = self.arc_w_closed()
+            if wc is None or self._n >= 2 ** 31 or len(self.src) >= 2 ** 31:
+                cache[key] = None
+            else:
+                i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(device)   # noqa: E731
+                f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(device)  # noqa: E731
+                pad = lambda t: t if t.numel() else t.new_zeros(1)                                # noqa: E731
+                cache[key] = dict(
+                    ptr=i32(self.ptr), ptr_ne=i32(self.ptr_ne), dst=pad(i32(self.dst)),
+                    ilabel=pad(i32(self.ilabel)), weight=pad(f64(self.weight)), w_closed=pad(f64(wc)),
+                    rank=i32(self.eps_rank()), nstates=self._n,
+                    max_rank=int(self.eps_rank().max()) if self._n else 0)
+        return cache[key]
+
     # ---- text format ---------------------------------------------------------
     @classmethod
     def read_text(cls, path, isymbols=None, osymbols=None, acceptor=False):

@@ -523,3 +523,147 @@ class DeviceBeamSearch(object):
         self.estimations = self._est[eff & 1][:, :eff].long()
         self.scores = self._scores[eff & 1]
         return self
+
+
+class DeviceBeamSearchLM(object):
+    """BeamSearchLM (reference beam_search.py:185-363) with ALL of its state on the MI355X, for any
+    number of utterances: B utterances behave as B independent BeamSearchLM(batch_size=1) runs,
+    each on its own `enc_lens[b]` encoder frames (the own length stands where the host class
+    reads `att_weights.size(0)`).  Per label step: `asr_lm_label_costs_f64` (LM cost of every
+    extension from the bags, fp64), `asr_beam_lm_step_f32` (scores, finish test, finished list,
+    best hypothesis, top-k, re-indexing, freeze) and `asr_lm_bag_advance_f64` (the survivors'
+    bags) — no host read-back.  An utterance whose finished list reached `beam_size` is frozen:
+    later launches change nothing of it.  `poll_finished` reads the frozen flags and the
+    bag-overflow word in one copy; `finalize` fills the attributes of the host class, each with
+    one entry per utterance (`finished`, `estimations`, `scores`, `coverage`, `fst_states` are
+    lists over the utterances).
+
+    Quirk of the host class kept on purpose: `best_finished_scores_elements` holds THIS step's
+    score elements (EOS column) at the beam index stored with `finished[0]`, which may have
+    joined the list steps ago, when that beam index meant another hypothesis."""
+
+    def __init__(self, lm, lm_weight, alphabet_mapping, min_attention_pos, coverage_tau,
+                 coverage_weight, batch_size, beam_size, device, num_classes, length_normalization,
+                 max_steps, max_frames, enc_lens, keep_eos_score=False):
+        from att_speech import _native
+        self._native = _native
+        self.lm, self.lm_weight = lm, float(lm_weight)
+        self.batch_size, self.beam_size, self.num_classes = batch_size, beam_size, num_classes
+        self.length_normalization = length_normalization
+        self.min_attention_pos = float(min_attention_pos)
+        self.coverage_tau, self.coverage_weight = float(coverage_tau), float(coverage_weight)
+        self.keep_eos_score = keep_eos_score
+        B, beam, cap, T = batch_size, beam_size, max_steps + 1, max_frames
+        hyps, bc = B * beam, _native.LM_BAG_CAP
+        i32 = dict(dtype=torch.int32, device=device)
+        z = lambda *s: torch.zeros(*s, device=device)  # noqa: E731
+        zi = lambda *s: torch.zeros(*s, **i32)  # noqa: E731
+        self._lens = torch.as_tensor(enc_lens).to(device, torch.int32).contiguous()
+        self._scores = [z(hyps), z(hyps)]
+        self._est = [zi(hyps, cap), zi(hyps, cap)]
+        self._cov = [z(hyps, T), z(hyps, T)] if self.coverage_weight > 0 else [None, None]
+        self._min_eos = torch.full((hyps,), float('-inf'), device=device) if keep_eos_score else None
+        self._use_lm = self.lm_weight != 0
+        self._lmdev = self._mapping = self._cost = None
+        self._bags = [None, None]
+        if self._use_lm:
+            self._lmdev = lm.device_arrays(device)
+            self._mapping = torch.as_tensor(list(alphabet_mapping)).to(device, torch.int32).contiguous()
+            self._cost = torch.zeros(hyps, num_classes, dtype=torch.float64, device=device)
+            for k in range(2):
+                self._bags[k] = (zi(hyps, bc), torch.zeros(hyps, bc, dtype=torch.float64, device=device),
+                                 zi(hyps))
+            self._bags[0][0][:, 0] = lm.start()         # every hypothesis starts as {start: 0}
+            self._bags[0][2][:] = 1
+        self._state = {
+            'fin_count': zi(B), 'fin_parity': zi(B), 'fin_score': z(2, B, beam),
+            'fin_len': zi(2, B, beam), 'fin_beam': zi(2, B, beam), 'fin_tokens': zi(2, B, beam, cap),
+            'best_score': torch.full((B,), float('-inf'), device=device), 'best_len': zi(B),
+            'best_tokens': zi(B, cap), 'best_elems': z(B, 3),
+            'new_input': zi(hyps), 'parent': zi(hyps),
+            # frozen [B] and the bag-overflow word behind it: one copy per poll
+            'flags': zi(B + 1), 'nsteps': zi(B)}
+        self._state['frozen'] = self._state['flags'][:B]
+        self._state['overflow'] = self._state['flags'][B:]
+        self._step = 0
+        self.overflow = 0
+        self.print_debug = False
+        self.estimations = None
+        self.coverage = None
+
+    def step(self, logits, att_weights, *args, **kwargs):
+        """logits [1, B*beam, C] or [B*beam, C]; att_weights [B*beam, T], this step's alignment ->
+        (chosen labels, parent hypothesis) as int32 device tensors (valid until the next step)."""
+        s, n, st = self._step, self._native, self._state
+        B, beam = self.batch_size, self.beam_size
+        logits = logits.reshape(-1, self.num_classes).contiguous()
+        att = att_weights.contiguous()
+        len_div = float(s ** self.length_normalization) if s > 0 else 1.0
+        i, o = s & 1, (s + 1) & 1
+        if self._use_lm:
+            n.lm_label_costs(self._lmdev, *self._bags[i], self._mapping, st['frozen'], B, beam,
+                             self.num_classes, self._cost)
+        n.beam_lm_step(logits, att, self._lens, self._cost, self.lm_weight, self._scores[i],
+                       self._scores[o], self._est[i], self._est[o], self._cov[i], self._cov[o],
+                       self._min_eos, s, B, beam, len_div, self.min_attention_pos, self.coverage_tau,
+                       self.coverage_weight, st)
+        if self._use_lm:
+            n.lm_bag_advance(self._lmdev, self._mapping, self._bags[i], self._bags[o], st['parent'],
+                             st['new_input'], st['nsteps'], s, B, beam, st['overflow'])
+        self._step = s + 1
+        return st['new_input'], st['parent']
+
+    def poll_finished(self):
+        """True when every utterance is frozen or a bag overflowed (`self.overflow` = its size)."""
+        flags = self._state['flags'].cpu().tolist()
+        self.overflow = int(flags[-1])
+        return self.overflow > 0 or all(flags[:-1])
+
+    has_finished = poll_finished
+
+    def get_graph(self):
+        return None
+
+    def finalize(self):
+        st = {k: v.cpu() for k, v in self._state.items()}
+        B, beam = self.batch_size, self.beam_size
+        self.overflow = int(st['overflow'][0])
+        eff = st['nsteps'].tolist()                  # steps that took effect, per utterance
+        lens = st['best_len'].tolist()
+        toks = st['best_tokens'].long()
+        self.best_finished = [toks[b, :lens[b]] if lens[b] > 0 else [] for b in range(B)]
+        self.best_finished_scores = [float(v) for v in st['best_score'].tolist()]
+        el = st['best_elems'].tolist()
+        self.best_finished_scores_elements = {'acoustic': [el[b][0] for b in range(B)],
+                                              'lm': [el[b][1] for b in range(B)]}
+        if self.coverage_weight > 0:
+            self.best_finished_scores_elements['coverage'] = [el[b][2] for b in range(B)]
+        par = st['fin_parity'].tolist()
+        self.finished = []
+        for b in range(B):
+            n = int(st['fin_count'][b])
+            self.finished.append([
+                (st['fin_score'][par[b], b, r],
+                 st['fin_tokens'][par[b], b, r, :int(st['fin_len'][par[b], b, r])].long(),
+                 int(st['fin_beam'][par[b], b, r])) for r in range(n)])
+        sl = lambda t, b: t[b * beam:(b + 1) * beam]  # noqa: E731
+        est = [e.cpu() for e in self._est]
+        sc = [s.cpu() for s in self._scores]
+        self.estimations = [sl(est[eff[b] & 1], b)[:, :eff[b]].long() for b in range(B)]
+        self.scores = [sl(sc[eff[b] & 1], b) for b in range(B)]
+        self.coverage = None
+        if self.coverage_weight > 0:
+            cov = [c.cpu() for c in self._cov]
+            ln = self._lens.cpu().tolist()
+            self.coverage = [sl(cov[eff[b] & 1], b)[:, :ln[b]].t() for b in range(B)]
+        self.fst_states = []
+        if self._use_lm:
+            bags = [[t.cpu() for t in bg] for bg in self._bags]
+            for b in range(B):
+                bs, bw, bn = bags[eff[b] & 1]
+                self.fst_states.append([
+                    dict(zip(bs[h, :int(bn[h])].tolist(), bw[h, :int(bn[h])].tolist()))
+                    for h in range(b * beam, (b + 1) * beam)])
+        else:
+            self.fst_states = [[] for _ in range(B)]
+        return self

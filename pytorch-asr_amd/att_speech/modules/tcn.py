@@ -23,6 +23,7 @@ arithmetic layout are this build's:
 from __future__ import absolute_import, division, print_function
 
 import os
+import warnings
 
 import torch
 import torch.nn.functional as F
@@ -451,12 +452,35 @@ class AttentionDecoderTCN(nn.Module):
         C, beam = self.num_classes, self.beam_size
         if os.environ.get('ASR_TCN_NATIVE', '1') == '0':     # A/B switch: torch ops + BeamSearch
             return False
-        return (encoded.is_cuda and not self.lm and not self.training
+        if self.lm and not self._native_lm_ok(encoded):
+            return False
+        return (encoded.is_cuda and not self.training
                 and not self.attn.force_forward and self.attn.kernel_size == 32
                 and 1 <= encoded.size(0) <= _STEP_MAX_FRAMES and beam <= 32 and beam * (C - 1) <= 2048 and encoded.dtype == torch.float32)
 
+    def _native_lm_ok(self, encoded):
+        """The device LM-fused search (DeviceBeamSearchLM) takes a model with an LM when the LM's
+        epsilon graph is acyclic, its labels fit the classes, and none of rescore / graph search /
+        forced-forward attention is asked for.  ASR_LM_BEAM_NATIVE, read per call: 0 keeps the host
+        BeamSearchLM (one utterance at a time), 1 takes the device search for every batch size;
+        unset, batches go to the device and a single utterance stays with the host class, which is
+        what it ran on before and against which the device search has not been timed yet."""
+        switch = os.environ.get('ASR_LM_BEAM_NATIVE', '')
+        if switch == '0' or (switch != '1' and encoded.size(1) == 1):
+            return False
+        if self.rescore or self.use_graph_search or self.attn.force_forward:
+            return False
+        if self.lm_weight == 0 and not self.coverage_weight > 0:
+            return False
+        lm = self.lm
+        if lm.eps_rank() is None or not len(lm.ilabel) or int(lm.ilabel.max()) >= self.num_classes:
+            return False
+        return bool(encoded.is_cuda and lm.device_arrays(encoded.device) is not None)
+
     def _decode_native(self, encoded, encoded_lens, return_attention, poll_every=8):
-        """The MI355X decode loop for the plain beam search: per label step the LM state of
+        """The MI355X decode loop, for the plain beam search and, with an LM, the LM-fused one
+        (DeviceBeamSearchLM: asr_lm_label_costs_f64, asr_beam_lm_step_f32, asr_lm_bag_advance_f64 in
+        place of asr_beam_step_f32; None when an LM bag outgrew the cap): per label step the LM state of
         the last frame as dense products (TCN.last_step), ONE launch for the local attention
         + context (asr_tcn_attention_step_f32), the output MLP, ONE launch for the beam
         bookkeeping (asr_beam_step_f32) — no host read-back inside a step; the all-finished
@@ -467,8 +491,16 @@ class AttentionDecoderTCN(nn.Module):
         beam, dev, attn = self.beam_size, encoded.device, self.attn
         hyps = B * beam
         lens = torch.as_tensor(encoded_lens).to(dev, torch.int32)
-        search = DeviceBeamSearch(B, beam, dev, self.num_classes, self.length_normalization,
-                                  self.TRANSCRIPTION_LEN_GUARD)
+        if self.lm:
+            from att_speech.modules.beam_search import DeviceBeamSearchLM
+            search = DeviceBeamSearchLM(
+                self.lm, self.lm_weight, self.alphabet_mapping, self.min_attention_pos,
+                self.coverage_tau, self.coverage_weight, B, beam, dev, self.num_classes,
+                self.length_normalization, self.TRANSCRIPTION_LEN_GUARD, T, lens,
+                keep_eos_score=self.keep_eos_score)
+        else:
+            search = DeviceBeamSearch(B, beam, dev, self.num_classes, self.length_normalization,
+                                      self.TRANSCRIPTION_LEN_GUARD)
         # per-utterance operands (the reference repeats them per hypothesis, :449-456)
         (eproj, _), first = attn.init_attention(encoded, lens)
         eproj = eproj.contiguous()
@@ -491,7 +523,7 @@ class AttentionDecoderTCN(nn.Module):
                 eproj, enc, lens, fg[:, :n_filt].contiguous(), fg[:, n_filt:].contiguous(),
                 w_score, b_score, attn.temperature, att, parent, beam)
             logits = self._step_output(lm_state, context)
-            chosen, parent = search.step(logits)
+            chosen, parent = search.step(logits, att)
             if return_attention:
                 trace_logits.append(logits.detach()[None])
                 trace_att.append(att.t().detach())
@@ -500,19 +532,58 @@ class AttentionDecoderTCN(nn.Module):
             if (return_attention or step % poll_every == poll_every - 1) and search.poll_finished():
                 break
         search.finalize()
+        if getattr(search, 'overflow', 0):
+            self._last_bag_overflow = search.overflow
+            return None                                  # an LM bag outgrew the device's cap
         out = {'decoded': search.best_finished,
                'decoded_scores': search.best_finished_scores_elements,
                'loss': torch.Tensor(search.best_finished_scores).mean()}
         if return_attention:
             out.update(attweights=trace_att, logits=trace_logits)
-        out.update(coverage=None, graph=None, beam_search=search)
+        out.update(coverage=search.coverage, graph=None, beam_search=search)
+        return out
+
+    def _decode_host_each(self, encoded, encoded_lens, return_attention):
+        """The host BeamSearchLM takes one utterance per call: a batch whose device search gave up
+        (an LM bag above the cap) is decoded utterance by utterance, each on its own frames, and the
+        results are joined (lists over the utterances; `beam_search`, `coverage`, `attweights` and
+        `logits` are lists of the per-utterance values)."""
+        lens = [int(v) for v in torch.as_tensor(encoded_lens).tolist()]
+        old = os.environ.get('ASR_LM_BEAM_NATIVE')
+        os.environ['ASR_LM_BEAM_NATIVE'] = '0'
+        try:
+            parts = [self.decode(encoded[:lens[b], b:b + 1].contiguous(), torch.tensor([lens[b]]),
+                                 return_attention=return_attention) for b in range(len(lens))]
+        finally:
+            if old is None:
+                del os.environ['ASR_LM_BEAM_NATIVE']
+            else:
+                os.environ['ASR_LM_BEAM_NATIVE'] = old
+        out = {'decoded': [p['decoded'][0] for p in parts],
+               'decoded_scores': {k: [p['decoded_scores'][k][0] for p in parts]
+                                  for k in parts[0]['decoded_scores']},
+               'loss': torch.stack([p['loss'] for p in parts]).mean()}
+        for k in ('attweights', 'logits', 'coverage', 'graph', 'beam_search'):
+            if k in parts[0]:
+                out[k] = [p[k] for p in parts]
+        out['graph'] = None
         return out
 
     def decode(self, encoded, encoded_lens, texts=None, text_lens=None,
                return_attention=False, print_debug=False, **kwargs):
         """Beam search over label steps (:476-585), at most TRANSCRIPTION_LEN_GUARD of them."""
         if self._native_decode_ok(encoded) and not print_debug:
-            return self._decode_native(encoded, encoded_lens, return_attention)
+            out = self._decode_native(encoded, encoded_lens, return_attention)
+            if out is not None:
+                return out
+            from att_speech import _native
+            if not _native._WARNED.get('lm_bag_overflow'):
+                _native._WARNED['lm_bag_overflow'] = True
+                warnings.warn('an LM bag of the device beam search asked for at least %d states, above '
+                              'its cap of %d: decoding this call with the host BeamSearchLM, one utterance at a time'
+                              % (self._last_bag_overflow, _native.LM_BAG_CAP))
+            if encoded.size(1) > 1:
+                return self._decode_host_each(encoded, encoded_lens, return_attention)
         search = self._make_search(encoded.size(1), encoded.device)
         search.print_debug = print_debug
         state = self.enc_initial_state(encoded, encoded_lens, self.beam_size, encoded.size(1))

@@ -1,0 +1,135 @@
+"""LM-fused decode of the TCN attention decoder, device search against host search (development
+tool; bench.py is the contract benchmark).  Decoder dimensions of egs/wsj/yamls/lattice_decoding/
+tcn.yaml (tcn_hidden_size 384, att_hidden_size 64, dilations [1, 2], 2 layers per block), random
+weights, a random encoder output of --frames frames, the shipped trigram character LM
+(tests/golden/G_char_tg_syms.fst.gz), beam 10, lm_weight 0.75, coverage_weight 0.8, coverage_tau
+0.25, and a fixed budget of 250 label steps (min_attention_pos above 1: nothing finishes, so both
+searches run every step).  The vocabulary is the LM's own symbol table in label order, so every LM
+label is below the number of classes.
+
+What the numbers are NOT: the cost of LM fusion.  The start state of the shipped LM has one epsilon
+arc and nothing else, and BeamSearchLM starts from the unclosed bag {start: 0} (as the reference
+does), so every bag is empty from the first label on, on the host and on the device alike: the LM
+term is the constant -0.75e20, which in fp32 absorbs every acoustic score (the top-k is a run of exact
+ties), and asr_lm_label_costs_f64 / asr_lm_bag_advance_f64 leave through their early exits.  The
+second configuration, `closed_start`, moves the LM's start to the state behind that epsilon arc, so
+that the bags hold the context state and its back-off chain and both LM kernels do their work.
+
+Device path (DeviceBeamSearchLM, ASR_LM_BEAM_NATIVE=1) at B in --batches; host path (ASR_LM_BEAM_NATIVE=0, BeamSearchLM,
+one utterance per call) looped over --host-utts of the same utterances.  Prints utterances/s with
+the spread over the timed calls and, with --out, writes them as JSON."""
+import argparse
+import datetime
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'pytorch-asr_amd'))
+
+from att_speech.lm_fst import LmFst                      # noqa: E402
+from att_speech.modules.tcn import AttentionDecoderTCN   # noqa: E402
+
+
+def lm_vocabulary(lm):
+    by_label = {k: s for k, s in lm.input_symbols()}
+    top = max(int(lm.ilabel.max()), max(by_label))
+    names = []
+    for k in range(top):                                  # class k <-> label k where the LM has one
+        s = by_label.get(k, '')
+        names.append(' ' if s == '<spc>' else s if s and s not in ('<eps>', '<s>', '</s>') else '<none%d>' % k)
+    return names
+
+
+def closed_start(lm):
+    """the same LM started behind the epsilon arc that is all its start state has"""
+    arcs = list(lm.arcs(lm.start()))
+    assert len(arcs) == 1 and arcs[0].ilabel == 0
+    return LmFst(lm.num_states(), arcs[0].nextstate, lm.src, lm.dst, lm.ilabel, lm.olabel, lm.weight,
+                 lm.final_w, lm.input_symbols(), lm.output_symbols())
+
+
+def run(a, dev, lm, name):
+    vocab = lm_vocabulary(lm)
+    torch.manual_seed(0)
+    dec = AttentionDecoderTCN(
+        {'features': torch.zeros(a.frames, 2, a.encoded)}, len(vocab), tcn_hidden_size=384,
+        att_hidden_size=64, dropout_p=0.3, kernel_size=3, dilation_sizes=[1, 2], tcn_layers_per_block=2,
+        beam_size=10, length_normalization=0.6, vocabulary=vocab, lm_file=lm, lm_weight=0.75,
+        coverage_weight=0.8, coverage_tau=0.25, min_attention_pos=2.0).eval().to(dev)
+    dec.TRANSCRIPTION_LEN_GUARD = a.steps
+    bmax = max(a.batches)
+    enc = torch.randn(a.frames, bmax, a.encoded, generator=torch.Generator().manual_seed(1)).to(dev)
+    res = {'device_path': {}, 'host_path': {}}
+
+    def stats(ups, **kw):
+        ups = sorted(ups)
+        return dict(utt_per_s_median=ups[len(ups) // 2], utt_per_s_min=ups[0], utt_per_s_max=ups[-1],
+                    calls=len(ups), **kw)
+    with torch.no_grad():
+        os.environ['ASR_LM_BEAM_NATIVE'] = '1'
+        for B in a.batches:
+            e, lens = enc[:, :B].contiguous(), torch.full((B,), a.frames)
+            out = dec.decode(e, lens)
+            assert type(out['beam_search']).__name__ == 'DeviceBeamSearchLM', type(out['beam_search'])
+            st = stats([B / t for t in timed(lambda: dec.decode(e, lens), a.iters)],
+                       largest_bag=max(len(d) for u in out['beam_search'].fst_states for d in u))
+            res['device_path'][str(B)] = st
+            print('%-13s device  B=%-4d %.2f utt/s (min %.2f max %.2f over %d calls; largest bag %d)' % (
+                name, B, st['utt_per_s_median'], st['utt_per_s_min'], st['utt_per_s_max'], st['calls'],
+                st['largest_bag']), flush=True)
+        os.environ['ASR_LM_BEAM_NATIVE'] = '0'
+        n = min(a.host_utts, bmax)
+
+        def host():
+            for b in range(n):
+                o = dec.decode(enc[:, b:b + 1].contiguous(), torch.tensor([a.frames]))
+            assert type(o['beam_search']).__name__ == 'BeamSearchLM'
+        st = stats([n / t for t in timed(host, max(1, a.iters - 1))], utterances_per_call=n)
+        res['host_path']['1'] = st
+        print('%-13s host    B=1    %.2f utt/s (min %.2f max %.2f over %d calls of %d utterances)' % (
+            name, st['utt_per_s_median'], st['utt_per_s_min'], st['utt_per_s_max'], st['calls'], n), flush=True)
+        del os.environ['ASR_LM_BEAM_NATIVE']
+    return res
+
+
+def timed(fn, n):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batches', type=int, nargs='+', default=[1, 16, 256])
+    ap.add_argument('--frames', type=int, default=125)
+    ap.add_argument('--encoded', type=int, default=320)
+    ap.add_argument('--steps', type=int, default=250)
+    ap.add_argument('--iters', type=int, default=3)
+    ap.add_argument('--host-utts', type=int, default=2)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    dev = torch.device('cuda:0')
+    shipped = LmFst.read(os.path.join(ROOT, 'tests', 'golden', 'G_char_tg_syms.fst.gz'))
+    res = {'date': datetime.date.today().isoformat(), 'device': torch.cuda.get_device_name(0),
+           'frames': a.frames, 'steps': a.steps, 'beam': 10, 'lm': 'G_char_tg_syms.fst.gz',
+           'lm_weight': 0.75, 'coverage_weight': 0.8, 'coverage_tau': 0.25, 'configurations': {}}
+    for name, lm in (('shipped', shipped), ('closed_start', closed_start(shipped))):
+        res['configurations'][name] = run(a, dev, lm, name)
+    if a.out:
+        with open(a.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
