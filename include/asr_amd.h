@@ -155,6 +155,9 @@ int asr_lattice_forward_f32(const float *lp, int T, int B, int C,
  * (modules/ctc_losses.py:29-43): group = C for the plain branch (:41-42),
  * group = num_symbols for normalize_by_dim = context_order-1 (:34-40,
  * the per-context block-wise normalisation over the last symbol axis).
+ * Computed as (x - max) - log sum exp(x - max): a common offset of the row costs no accuracy.
+ * -inf entries (masked classes) give -inf; a row of nothing but -inf gives NaN (-inf - -inf),
+ * as torch.log_softmax does.  group <= 8192, else ASR_EUNSUPPORTED (all row kernels below too).
  */
 int asr_log_softmax_fwd_f32(const float *x, int64_t rows, int group,
                             float *y, void *stream);
@@ -168,7 +171,8 @@ int asr_log_softmax_bwd_f32(const float *y, const float *dy, int64_t rows,
  *   row_max[t,b] = max_c x[t,b,c];  y = x - row_max;
  *   max_sum[b]   = sum_{t < lens[b]} row_max[t,b]
  * x, y [T,B,C]; row_max [T,B] (required, also the reduction scratch);
- * max_sum [B], summed in a fixed order (bitwise reproducible).
+ * max_sum [B], summed in a fixed order (bitwise reproducible); lens outside [0, T] are
+ * clamped.  A row of nothing but -inf has row_max -inf and y NaN.
  */
 int asr_sub_rowmax_f32(const float *x, int T, int B, int C,
                        const int32_t *lens, float *y, float *row_max,
@@ -177,7 +181,9 @@ int asr_sub_rowmax_f32(const float *x, int T, int B, int C,
 /*
  * Index of the first maximum of every row of x [rows, C]: the per-frame
  * arg-max of CTCDecoderAdvanced.decode (advanced_decoder.py:352,
- * `torch.max(logits_t, 2)`).  out_idx [rows] i32.
+ * `torch.max(logits_t, 2)`).  out_idx [rows] i32.  Equal values: the lowest index, so a row
+ * of nothing but -inf gives 0.  A NaN entry ranks as -inf (torch.max would return it): the
+ * result is the first maximum of the other entries, and 0 for a row of nothing but NaN.
  */
 int asr_argmax_rows_f32(const float *x, int64_t rows, int C, int32_t *out_idx,
                         void *stream);
@@ -455,6 +461,8 @@ int asr_bn_act_bwd_phase_f32(const void *x, int x_bf16, const float *conv_bias, 
  * frames t < lens[b] of nls — the value the reference subtracts as its denominator when
  * denominator_red = 'none'.  bwd: dx = dy - exp(y + nls) * sum_c dy, the gradient of the
  * log-softmax (the reference detaches the maximum), from the shifted y itself.
+ * y is the fp32 difference x - max_c x, correctly rounded; -inf entries stay -inf and take no
+ * gradient; a row of nothing but -inf gives y = NaN and nls = NaN.  lens as in asr_sub_rowmax_f32.
  */
 int asr_log_softmax_shift_fwd_f32(const float *x, int T, int B, int C, const int32_t *lens,
                                   float *y, float *nls, float *nls_sum, void *stream);
@@ -474,7 +482,8 @@ int asr_log_softmax_shift_bwd_split_bf16(const float *y, const float *nls, const
 /*
  * out[e] = sum over g < G of in[g * n + e] (n % 4 == 0): the sum of the partial products of a
  * weight-gradient GEMM split over chunks of frames (torch's strided reduction reads at
- * 1.4 TB/s here).
+ * 1.4 TB/s here).  Summed over g in that order in fp32 (bitwise reproducible).  in and out
+ * must be 16-byte aligned (float4 accesses), else ASR_EINVAL.
  */
 int asr_sum_leading_f32(const float *in, int G, int64_t n, float *out, void *stream);
 
@@ -486,6 +495,9 @@ int asr_sum_leading_f32(const float *in, int G, int64_t n, float *out, void *str
  *   x [rows, cols] f32 with row stride ldx (elements); hi / lo [rows, cols] bf16 with row
  *   strides ldhi / ldlo — strided so that the halves can be written straight into the
  *   K-concatenated operand [rows, 3 cols].  A contiguous tensor is one row of n elements.
+ * Zeros keep their sign in hi (lo = +0), denormals are split like any value, NaN gives NaN in
+ * both halves.  hi + lo is NOT x for +-inf (hi = +-inf, lo = inf - inf = NaN) nor for finite
+ * |x| >= 0x7f7f8000 (3.3961775e38), which round to hi = +-inf with lo = -+inf.
  * (ABI v14)
  */
 int asr_split_bf16_f32(const float *x, int64_t rows, int64_t cols, int64_t ldx,

@@ -1363,10 +1363,13 @@ def split_bf16(x, hi=None, lo=None):
 
 
 def sum_leading(t):
-    """asr_sum_leading_f32: t [G, ...] f32 contiguous on the GPU -> t.sum(0)"""
+    """asr_sum_leading_f32: t [G, ...] f32 contiguous on the GPU -> t.sum(0); torch's own sum for
+    what the kernel does not take (n % 4 != 0, a view that does not start on 16 bytes)"""
     if not t.is_cuda or t.dtype != torch.float32 or (t[0].numel() & 3):
         return t.sum(0)
     t = t.contiguous()
+    if t.data_ptr() & 15:
+        return t.sum(0)
     out = torch.empty(t.shape[1:], dtype=torch.float32, device=t.device)
     check(lib().asr_sum_leading_f32(_p(t), t.shape[0], t[0].numel(), _p(out), _stream()),
           'asr_sum_leading_f32')

@@ -38,12 +38,14 @@ __global__ void log_softmax_fwd_kernel(const float *__restrict__ x,
 #pragma unroll
         for (int i = 0; i < PER; ++i) s += __expf(v[i] - m);
         s = wave_sum(s);
-        const float l = m + __logf(s);
+        // (x - m) - log s, not x - (m + log s): the latter rounds log s to an ulp of m, which
+        // costs 5e-4 of every value of a row at a common offset of 1e4
+        const float ls = __logf(s);
         float *yr = y + r * group;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             int c = i * 64 + lane;
-            if (c < group) yr[c] = v[i] - l;
+            if (c < group) yr[c] = (v[i] - m) - ls;
         }
     }
 }
@@ -139,6 +141,7 @@ __global__ void argmax_rows_kernel(const float *__restrict__ x,
         for (int i = 0; i < PER; ++i) {
             int c = i * 64 + lane;
             float v = c < C ? xr[c] : -INFINITY;
+            v = v != v ? -INFINITY : v;       // a NaN ranks as -inf: it would stop every comparison below
             if (c < C && (v > best || arg == 0x7fffffff)) { best = v; arg = c; }
         }
 #pragma unroll
@@ -247,6 +250,7 @@ __global__ __launch_bounds__(256) void sum_leading_kernel(const float4 *in, int 
 
 extern "C" int asr_sum_leading_f32(const float *in, int G, int64_t n, float *out, void *stream) {
     if (!in || !out || G <= 0 || n <= 0 || (n & 3)) return ASR_EINVAL;
+    if ((((uintptr_t)in | (uintptr_t)out) & 15) != 0) return ASR_EINVAL;    // 16-byte loads and stores
     const int64_t n4 = n >> 2;
     hipLaunchKernelGGL(sum_leading_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, (const float4 *)in, G, n4, (float4 *)out);
