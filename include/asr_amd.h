@@ -574,6 +574,37 @@ int asr_tcn_attention_step_f32(const float *eproj, const float *enc, const int32
                                float *att_new, float *context, void *stream);
 
 /*
+ * The same step under LocalAttention's force_forward = (win_lo, win_hi) (an addition to ABI
+ * v24; replaces recompute_forward_mask, reference att_speech/modules/tcn.py:165-188, and its
+ * use in LocalAttention.forward, :226-228, together with what the entry above replaces).
+ * Operands as above, plus the window.  With a = att_prev[parent[h]] (att_prev[h] when parent
+ * is null):
+ *   peak  = max_t a[t] over all T frames, where = the LOWEST t that attains it (ties go to the
+ *           first maximum, as torch.max over a row gives them)
+ *   active = peak >= 0.1f  (the reference's `att_max.item() < 0.1` negated; no fp32 value lies
+ *           between 0.1 and 0.1f)
+ *   mask_t = (t >= enc_lens[u] ? -1e5 : 0)
+ *          + (active && (t < where + win_lo || t >= where + win_hi) ? -1e5 : 0)
+ *   att_new = softmax_t( (w . tanh(...) + b) * temperature + mask_t ),  context as above.
+ * A frame that is both padded and outside the window carries -2e5.  Only the frames with the
+ * fewest masks can get a weight (exp(-1e5 + O(100)) is an exact zero in every format): the
+ * kernel evaluates scores and context on those frames alone and writes an exact 0.0f to every
+ * other frame of att_new.  A window clipped to nothing, or lying wholly at or behind enc_lens,
+ * leaves the softmax over frames that all carry one -1e5 (two, when enc_lens is 0 as well); a
+ * diffuse row (peak < 0.1f) is treated as by the entry above.
+ * Limits: those of the entry above; win_lo >= win_hi or win_hi < 1 is ASR_EUNSUPPORTED (with
+ * win_hi < 1 the reference's `mask[right:]` takes a negative slice index and means something
+ * else).
+ */
+int asr_tcn_attention_step_win_f32(const float *eproj, const float *enc, const int32_t *enc_lens,
+                                   const float *filt, const float *glob, const float *w_score,
+                                   float b_score, float temperature,
+                                   const float *att_prev, const int32_t *parent,
+                                   int T, int B, int beam, int A, int Kf, int E,
+                                   int win_lo, int win_hi,
+                                   float *att_new, float *context, void *stream);
+
+/*
  * The training recurrence of the same local attention over all label positions (ABI v24;
  * replaces the per-position loop of AttentionDecoderTCN.forward, reference
  * att_speech/modules/tcn.py:357-440, over LocalAttention.scores / forward, :190-230, and the

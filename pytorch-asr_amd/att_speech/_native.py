@@ -79,6 +79,8 @@ _SIGNATURES = {
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),
     'asr_tcn_attention_step_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp,
                                         _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'asr_tcn_attention_step_win_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp,
+                                            _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'asr_tcn_attention_scan_fwd_f32': (_i, [_vp] * 6 + [_f, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'asr_tcn_attention_scan_bwd_f32': (_i, [_vp] * 5 + [_f, _vp, _vp, _vp, _i, _i, _i, _i, _i] +
                                        [_vp] * 6),
@@ -1034,8 +1036,9 @@ def bn_act_bwd(x, gamma, beta, mean, invstd, training, lo, hi, dy, time_major=Fa
 
 
 def tcn_attention_step(eproj, enc, enc_lens, filt, glob, w_score, b_score, temperature,
-                       att_prev, parent, beam):
-    """asr_tcn_attention_step_f32 -> (att_new [B*beam, T], context [B*beam, E])."""
+                       att_prev, parent, beam, window=None):
+    """asr_tcn_attention_step_f32 -> (att_new [B*beam, T], context [B*beam, E]); with
+    `window` = (lo, hi), LocalAttention's force_forward, asr_tcn_attention_step_win_f32."""
     eproj, enc = _dev(eproj, torch.float32, 'eproj'), _dev(enc, torch.float32, 'enc')
     filt, glob = _dev(filt, torch.float32, 'filt'), _dev(glob, torch.float32, 'glob')
     att_prev = _dev(att_prev, torch.float32, 'att_prev')
@@ -1048,6 +1051,15 @@ def tcn_attention_step(eproj, enc, enc_lens, filt, glob, w_score, b_score, tempe
     att_new = torch.empty((hyps, T), dtype=torch.float32, device=enc.device)
     ctx = torch.empty((hyps, E), dtype=torch.float32, device=enc.device)
     par = None if parent is None else _dev(parent, torch.int32, 'parent')
+    if window is not None:
+        lo, hi = window
+        if int(lo) != lo or int(hi) != hi:
+            raise TypeError("window must be a pair of integers")
+        check(lib().asr_tcn_attention_step_win_f32(
+            _p(eproj), _p(enc), _p(enc_lens), _p(filt), _p(glob), _p(w_score), float(b_score),
+            float(temperature), _p(att_prev), _p(par), T, B, beam, A, taps, E, int(lo), int(hi),
+            _p(att_new), _p(ctx), _stream()), 'asr_tcn_attention_step_win_f32')
+        return att_new, ctx
     check(lib().asr_tcn_attention_step_f32(
         _p(eproj), _p(enc), _p(enc_lens), _p(filt), _p(glob), _p(w_score), float(b_score),
         float(temperature), _p(att_prev), _p(par), T, B, beam, A, taps, E, _p(att_new), _p(ctx),

@@ -448,6 +448,23 @@ class AttentionDecoderTCN(nn.Module):
                                keep_eos_score=self.keep_eos_score)
         return BeamSearchLM(*fused, keep_eos_score=self.keep_eos_score)
 
+    def _native_window_ok(self):
+        """The device decode step takes no window, or a force_forward (lo, hi) of integers with
+        lo < hi and hi >= 1 (asr_tcn_attention_step_win_f32; with hi < 1 the reference's
+        `mask[right:]` takes a negative index, which stays with the torch path).
+        ASR_TCN_FF_NATIVE=0, read per call, sends every windowed model to the torch path."""
+        window = self.attn.force_forward
+        if not window:
+            return True
+        if os.environ.get('ASR_TCN_FF_NATIVE', '1') == '0':
+            return False
+        try:
+            lo, hi = window
+        except (TypeError, ValueError):
+            return False
+        integral = all(isinstance(v, int) and not isinstance(v, bool) for v in (lo, hi))
+        return integral and lo < hi and hi >= 1
+
     def _native_decode_ok(self, encoded):
         C, beam = self.num_classes, self.beam_size
         if os.environ.get('ASR_TCN_NATIVE', '1') == '0':     # A/B switch: torch ops + BeamSearch
@@ -455,20 +472,21 @@ class AttentionDecoderTCN(nn.Module):
         if self.lm and not self._native_lm_ok(encoded):
             return False
         return (encoded.is_cuda and not self.training
-                and not self.attn.force_forward and self.attn.kernel_size == 32
+                and self._native_window_ok() and self.attn.kernel_size == 32
                 and 1 <= encoded.size(0) <= _STEP_MAX_FRAMES and beam <= 32 and beam * (C - 1) <= 2048 and encoded.dtype == torch.float32)
 
     def _native_lm_ok(self, encoded):
         """The device LM-fused search (DeviceBeamSearchLM) takes a model with an LM when the LM's
-        epsilon graph is acyclic, its labels fit the classes, and none of rescore / graph search /
-        forced-forward attention is asked for.  ASR_LM_BEAM_NATIVE, read per call: 0 keeps the host
+        epsilon graph is acyclic, its labels fit the classes, neither rescore nor graph search is
+        asked for, and a force_forward window is one the device step takes (_native_window_ok).
+        ASR_LM_BEAM_NATIVE, read per call: 0 keeps the host
         BeamSearchLM (one utterance at a time), 1 takes the device search for every batch size;
         unset, batches go to the device and a single utterance stays with the host class, which is
         what it ran on before and against which the device search has not been timed yet."""
         switch = os.environ.get('ASR_LM_BEAM_NATIVE', '')
         if switch == '0' or (switch != '1' and encoded.size(1) == 1):
             return False
-        if self.rescore or self.use_graph_search or self.attn.force_forward:
+        if self.rescore or self.use_graph_search or not self._native_window_ok():
             return False
         if self.lm_weight == 0 and not self.coverage_weight > 0:
             return False
@@ -482,7 +500,8 @@ class AttentionDecoderTCN(nn.Module):
         (DeviceBeamSearchLM: asr_lm_label_costs_f64, asr_beam_lm_step_f32, asr_lm_bag_advance_f64 in
         place of asr_beam_step_f32; None when an LM bag outgrew the cap): per label step the LM state of
         the last frame as dense products (TCN.last_step), ONE launch for the local attention
-        + context (asr_tcn_attention_step_f32), the output MLP, ONE launch for the beam
+        + context (asr_tcn_attention_step_f32, or asr_tcn_attention_step_win_f32 under a
+        force_forward window), the output MLP, ONE launch for the beam
         bookkeeping (asr_beam_step_f32) — no host read-back inside a step; the all-finished
         flag is polled every `poll_every` steps (steps behind the flag change nothing)."""
         from att_speech import _native
@@ -514,6 +533,7 @@ class AttentionDecoderTCN(nn.Module):
         b_score = float(attn.hidden_to_score.bias)
         history = enc.new_zeros(self.tcn.eff_history, hyps, self.tcn_hidden_size)
         parent = None
+        window = tuple(attn.force_forward) if attn.force_forward else None
         trace_att = [first.repeat_interleave(beam, dim=1).detach()] if return_attention else None
         trace_logits = []
         for step in range(self.TRANSCRIPTION_LEN_GUARD):
@@ -521,7 +541,7 @@ class AttentionDecoderTCN(nn.Module):
             fg = torch.addmm(b_att, lm_state, w_att.t())
             att, context = _native.tcn_attention_step(
                 eproj, enc, lens, fg[:, :n_filt].contiguous(), fg[:, n_filt:].contiguous(),
-                w_score, b_score, attn.temperature, att, parent, beam)
+                w_score, b_score, attn.temperature, att, parent, beam, window=window)
             logits = self._step_output(lm_state, context)
             chosen, parent = search.step(logits, att)
             if return_attention:

@@ -8,6 +8,11 @@
 //      encoder frames, context = sum_t a_t enc_t.  The reference runs this as a grouped
 //      conv1d with B*beam groups and ~12 elementwise / reduction launches.
 //
+//  asr_tcn_attention_step_win_f32 — the same step under LocalAttention's force_forward window
+//      (reference att_speech/modules/tcn.py:165-188, :226-228): frames outside
+//      [peak + lo, peak + hi) of the parent's previous alignment carry another -1e5 unless
+//      that alignment is diffuse.  Evaluated on the frames that can get a weight only.
+//
 //  asr_beam_step_f32 — BeamSearch.step (reference att_speech/modules/beam_search.py:
 //      58-124, 147-175) for every utterance in ONE launch and WITHOUT a host read-back:
 //      log-softmax, running scores, best-EOS bookkeeping with length normalisation
@@ -105,6 +110,169 @@ __global__ __launch_bounds__(ATT_NT) void tcn_attention_step_kernel(AttParams p)
             acc1 = fmaf(anew[t + 1], col[(size_t)(t + 1) * ts], acc1);
         }
         if (t < T) acc0 = fmaf(anew[t], col[(size_t)t * ts], acc0);
+        p.context[(size_t)h * E + e0] = acc0 + acc1;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The step under a force_forward window (lo, hi).  With a = the parent's previous alignment,
+// peak = max_t a[t] and `where` its first position, the window is active when peak >= 0.1f
+// (the reference tests `att_max.item() < 0.1` on an fp32 value against the double 0.1; no fp32
+// value lies between the double 0.1 and 0.1f, its nearest fp32 neighbour from above, so the
+// negation is the same test as >= 0.1f).  Frame t carries m(t) masks of -1e5 each:
+//     m(t) = [t >= len] + [active and (t < where + lo or t >= where + hi)]
+// Only the frames with m(t) = M = min_t m(t) can get a weight: exp(-1e5 + O(100)) underflows to
+// an exact zero in every format, which is what the padding test of the kernel above already
+// rests on.  With lenc = clamp(len, 0, T) and the clipped window [ws, we) =
+// [clamp(where + lo, 0, T), clamp(where + hi, 0, T)) (active rows; [0, T) for a diffuse row):
+//     M = 0, support [ws, min(we, lenc))          when that interval is not empty
+//     M = 1, support [0, lenc) u [ws, we)         otherwise, when this union is not empty: no
+//            window frame lies below lenc, so the window, if it has frames at all, starts at or
+//            behind lenc, where every one of its frames is padded (one mask), and every frame
+//            below lenc is outside it (one mask).  The two pieces need not touch: a peak among
+//            the padded frames leaves doubly masked frames between them
+//     M = 2, support [0, T)                       when both are empty (lenc = 0 and the window
+//            clipped to nothing): every frame is padded and outside
+// A diffuse row has M = 0 on [0, lenc), or M = 1 on [0, T) when lenc = 0.  The support is kept as
+// two intervals P = [p0, p1) and Q = [q0, q1) behind it; frame number i of the support lives at
+// anew[i].  The mask is added to the scores in fp32, so the scores of a masked support are
+// rounded to the grid of 1e5 (2^-7) here as they are in the reference.  For M = 1 that is the
+// reference's own single rounding; for M = 2 the kernel adds -2e5f once where the torch path
+// adds -1e5 to the padding term and the sum to the score, which can land one grid step (2^-6
+// near 2e5) away.
+struct AttWinParams {
+    AttParams a;
+    int win_lo, win_hi;
+    int split;          // LDS holds ATT_NT more floats: the channels may be spread over waves
+};
+
+__global__ __launch_bounds__(ATT_NT) void tcn_attention_step_win_kernel(AttWinParams pw) {
+    extern __shared__ float smem[];
+    const AttParams &p = pw.a;
+    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int u = h / p.beam;
+    const int T = p.T, A = p.A, E = p.E;
+    float *aprev = smem;                  // [KF - 1 zeros][T]
+    float *anew = smem + (KF - 1) + T;    // [T], the support's frames packed at the front
+    float *red = anew + T;                // [32]
+    float *part = red + 32;               // [ATT_NT] when pw.split
+    const int src = p.parent ? p.parent[h] : h;
+    const float *ap = p.att_prev + (size_t)src * T;
+    for (int i = tid; i < KF - 1 + T; i += ATT_NT) aprev[i] = i < KF - 1 ? 0.f : ap[i - (KF - 1)];
+    __syncthreads();
+
+    // peak of the parent's row and its FIRST position (torch.max over a row; a row without any
+    // value above -inf, or of NaNs, has no peak and counts as diffuse)
+    float pv = -INFINITY;
+    int pi = 0x7fffffff;
+    for (int t = tid; t < T; t += ATT_NT) {
+        const float v = aprev[KF - 1 + t];
+        if (v > pv) { pv = v; pi = t; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(pv, o, 64);
+        const int oi = __shfl_xor(pi, o, 64);
+        if (ov > pv || (ov == pv && oi < pi)) { pv = ov; pi = oi; }
+    }
+    int *redi = reinterpret_cast<int *>(red + 8);
+    if (lane == 0) { red[wave] = pv; redi[wave] = pi; }
+    __syncthreads();
+    pv = red[0]; pi = redi[0];
+    for (int w = 1; w < ATT_NT / 64; ++w)
+        if (red[w] > pv || (red[w] == pv && redi[w] < pi)) { pv = red[w]; pi = redi[w]; }
+
+    const int len = p.enc_lens[u];
+    const int lenc = min(max(len, 0), T);
+    int p0 = 0, p1 = lenc, q0 = 0, q1 = 0, M = 0;
+    if (pv >= 0.1f) {
+        const long lo = (long)pi + pw.win_lo, hi = (long)pi + pw.win_hi;
+        const int ws = (int)min(max(lo, 0L), (long)T), we = (int)min(max(hi, 0L), (long)T);
+        if (ws < min(we, lenc)) {
+            p0 = ws; p1 = min(we, lenc);
+        } else {
+            M = 1;
+            if (ws < we) { q0 = ws; q1 = we; }
+        }
+    }
+    if (p1 - p0 + q1 - q0 == 0) { M += 1; p0 = 0; p1 = T; }
+    const int n1 = p1 - p0, n = n1 + (q1 - q0);
+    const float mask = M == 0 ? 0.f : M == 1 ? -1e5f : -2e5f;
+    auto frame = [&](int i) -> int { return i < n1 ? p0 + i : q0 + (i - n1); };
+
+    // A support narrower than the workgroup leaves waves idle: up to 64 frames the A channels go
+    // to four waves, up to 128 to two (wave-uniform channel, so the filter addresses stay
+    // wave-uniform); the partial scores meet in LDS and are added in a fixed order.
+    const int parts = !pw.split ? 1 : n <= 64 ? 4 : n <= 128 ? 2 : 1;
+    const int per = ATT_NT / parts;
+    const int q = __builtin_amdgcn_readfirstlane(tid / per), f = tid % per;
+
+    const float *__restrict__ filt = p.filt + (size_t)h * A * KF;      // wave-uniform addresses
+    const float *__restrict__ glob = p.glob + (size_t)h * A;
+    float emax = -INFINITY;
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const int i = i0 + f;
+        const bool on = i < n;
+        const int t = on ? frame(i) : 0;
+        float win[KF];
+#pragma unroll
+        for (int j = 0; j < KF; ++j) win[j] = on ? aprev[t + j] : 0.f;   // a_prev[t - (KF-1) + j]
+        const float *ep = p.eproj + ((size_t)t * p.B + u) * A;
+        float e = 0.f;
+        for (int c = q; c < A; c += parts) {
+            float hid = ep[c] + glob[c];
+            const float *fc = filt + c * KF;
+#pragma unroll
+            for (int j = 0; j < KF; ++j) hid = fmaf(win[j], fc[j], hid);
+            const float ex = __expf(2.f * hid);
+            const float th = 1.f - 2.f / (ex + 1.f);
+            e = fmaf(p.w_score[c], th, e);
+        }
+        if (parts > 1) {                  // (n <= per: this loop runs once)
+            part[tid] = e;
+            __syncthreads();
+            if (q == 0) {
+                e = part[f] + part[per + f];
+                if (parts == 4) e = (e + part[2 * per + f]) + part[3 * per + f];
+            }
+        }
+        if (q == 0 && on) {
+            e = (e + p.b_score) * p.temperature + mask;
+            anew[i] = e;
+            emax = fmaxf(emax, e);
+        }
+    }
+    emax = block_max(emax, red);
+    float sum = 0.f;
+    for (int i = tid; i < n; i += ATT_NT) {
+        const float v = __expf(anew[i] - emax);
+        anew[i] = v;
+        sum += v;
+    }
+    sum = block_sum(sum, red);
+    const float inv = 1.f / sum;
+    float *out = p.att_new + (size_t)h * T;
+    for (int t = tid; t < T; t += ATT_NT) {
+        const int i = t >= p0 && t < p1 ? t - p0 : t >= q0 && t < q1 ? n1 + (t - q0) : -1;
+        float v = 0.f;                    // off the support: an exact zero
+        if (i >= 0) {
+            v = anew[i] * inv;
+            anew[i] = v;
+        }
+        out[t] = v;
+    }
+    __syncthreads();
+    // context over the support only
+    for (int e0 = tid; e0 < E; e0 += ATT_NT) {
+        const float *col = p.enc + (size_t)u * E + e0;
+        const size_t ts = (size_t)p.B * E;
+        float acc0 = 0.f, acc1 = 0.f;
+        int i = 0;
+        for (; i + 1 < n; i += 2) {
+            acc0 = fmaf(anew[i], col[(size_t)frame(i) * ts], acc0);
+            acc1 = fmaf(anew[i + 1], col[(size_t)frame(i + 1) * ts], acc1);
+        }
+        if (i < n) acc0 = fmaf(anew[i], col[(size_t)frame(i) * ts], acc0);
         p.context[(size_t)h * E + e0] = acc0 + acc1;
     }
 }
@@ -289,6 +457,38 @@ extern "C" int asr_tcn_attention_step_f32(const float *eproj, const float *enc,
     p.att_new = att_new; p.context = context;
     hipLaunchKernelGGL(tcn_attention_step_kernel, dim3(B * beam), dim3(ATT_NT), lds,
                        (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+}
+
+extern "C" int asr_tcn_attention_step_win_f32(const float *eproj, const float *enc,
+                                              const int32_t *enc_lens, const float *filt,
+                                              const float *glob, const float *w_score,
+                                              float b_score, float temperature,
+                                              const float *att_prev, const int32_t *parent,
+                                              int T, int B, int beam, int A, int Kf, int E,
+                                              int win_lo, int win_hi,
+                                              float *att_new, float *context, void *stream) {
+    if (T <= 0 || B <= 0 || beam <= 0 || A <= 0 || E <= 0) return ASR_EINVAL;
+    if (Kf != KF) return ASR_EUNSUPPORTED;
+    if (!eproj || !enc || !enc_lens || !filt || !glob || !w_score || !att_prev || !att_new ||
+        !context)
+        return ASR_EINVAL;
+    // hi < 1: the reference's mask[right:] would take a negative slice index
+    if (win_lo >= win_hi || win_hi < 1) return ASR_EUNSUPPORTED;
+    size_t lds = (size_t)(KF - 1 + 2 * T + 32) * sizeof(float);
+    if (lds > 64 * 1024) return ASR_EUNSUPPORTED;
+    AttWinParams pw;
+    AttParams &p = pw.a;
+    p.eproj = eproj; p.enc = enc; p.filt = filt; p.glob = glob; p.w_score = w_score;
+    p.att_prev = att_prev; p.enc_lens = enc_lens; p.parent = parent;
+    p.T = T; p.B = B; p.beam = beam; p.A = A; p.E = E;
+    p.b_score = b_score; p.temperature = temperature;
+    p.att_new = att_new; p.context = context;
+    pw.win_lo = win_lo; pw.win_hi = win_hi;
+    pw.split = lds + ATT_NT * sizeof(float) <= 64 * 1024;   // (T <= 8032: not for the last 128 values of T)
+    if (pw.split) lds += ATT_NT * sizeof(float);
+    hipLaunchKernelGGL(tcn_attention_step_win_kernel, dim3(B * beam), dim3(ATT_NT), lds,
+                       (hipStream_t)stream, pw);
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
 }
 

@@ -17,7 +17,13 @@ that the bags hold the context state and its back-off chain and both LM kernels 
 
 Device path (DeviceBeamSearchLM, ASR_LM_BEAM_NATIVE=1) at B in --batches; host path (ASR_LM_BEAM_NATIVE=0, BeamSearchLM,
 one utterance per call) looped over --host-utts of the same utterances.  Prints utterances/s with
-the spread over the timed calls and, with --out, writes them as JSON."""
+the spread over the timed calls and, with --out, writes them as JSON.
+
+--force-forward LO HI and --no-learnable-init decode under LocalAttention's window as the
+reference's readme does; --score-scale X draws the attention's score vector (zero at
+initialisation: uniform, hence diffuse alignments and an inactive window) from N(0, X^2 / A), and
+the fraction of (step, hypothesis) rows with an active window is reported.  --configs selects
+among `shipped` and `closed_start`."""
 import argparse
 import datetime
 import json
@@ -59,7 +65,13 @@ def run(a, dev, lm, name):
         {'features': torch.zeros(a.frames, 2, a.encoded)}, len(vocab), tcn_hidden_size=384,
         att_hidden_size=64, dropout_p=0.3, kernel_size=3, dilation_sizes=[1, 2], tcn_layers_per_block=2,
         beam_size=10, length_normalization=0.6, vocabulary=vocab, lm_file=lm, lm_weight=0.75,
-        coverage_weight=0.8, coverage_tau=0.25, min_attention_pos=2.0).eval().to(dev)
+        coverage_weight=0.8, coverage_tau=0.25, min_attention_pos=2.0,
+        att_force_forward=tuple(a.force_forward) if a.force_forward else None,
+        learnable_initial_attention=not a.no_learnable_init).eval()
+    if a.score_scale > 0:
+        with torch.no_grad():
+            dec.attn.hidden_to_score.weight.normal_(0.0, a.score_scale / 64 ** 0.5)
+    dec = dec.to(dev)
     dec.TRANSCRIPTION_LEN_GUARD = a.steps
     bmax = max(a.batches)
     enc = torch.randn(a.frames, bmax, a.encoded, generator=torch.Generator().manual_seed(1)).to(dev)
@@ -74,12 +86,20 @@ def run(a, dev, lm, name):
         for B in a.batches:
             e, lens = enc[:, :B].contiguous(), torch.full((B,), a.frames)
             out = dec.decode(e, lens)
-            assert type(out['beam_search']).__name__ == 'DeviceBeamSearchLM', type(out['beam_search'])
+            # (a list of host searches when a switch such as ASR_TCN_FF_NATIVE=0 closed the device gate)
+            searches = out['beam_search'] if isinstance(out['beam_search'], list) else [out['beam_search']]
+            kind = type(searches[0]).__name__
+            active = 0.0
+            if a.force_forward:
+                traced = dec.decode(e, lens, return_attention=True)
+                active = float((torch.stack(traced['attweights'][:-1]).max(1)[0] >= 0.1).float().mean())
             st = stats([B / t for t in timed(lambda: dec.decode(e, lens), a.iters)],
-                       largest_bag=max(len(d) for u in out['beam_search'].fst_states for d in u))
+                       largest_bag=(max(len(d) for u in searches[0].fst_states for d in u)
+                                    if kind == 'DeviceBeamSearchLM' else -1),
+                       window_active=active, search=kind)
             res['device_path'][str(B)] = st
-            print('%-13s device  B=%-4d %.2f utt/s (min %.2f max %.2f over %d calls; largest bag %d)' % (
-                name, B, st['utt_per_s_median'], st['utt_per_s_min'], st['utt_per_s_max'], st['calls'],
+            print('%-13s %-18s B=%-4d %.2f utt/s (min %.2f max %.2f over %d calls; largest bag %d)' % (
+                name, kind, B, st['utt_per_s_median'], st['utt_per_s_min'], st['utt_per_s_max'], st['calls'],
                 st['largest_bag']), flush=True)
         os.environ['ASR_LM_BEAM_NATIVE'] = '0'
         n = min(a.host_utts, bmax)
@@ -117,14 +137,21 @@ def main():
     ap.add_argument('--iters', type=int, default=3)
     ap.add_argument('--host-utts', type=int, default=2)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--force-forward', type=int, nargs=2, metavar=('LO', 'HI'), default=None)
+    ap.add_argument('--no-learnable-init', action='store_true')
+    ap.add_argument('--score-scale', type=float, default=0.0)
+    ap.add_argument('--configs', nargs='+', default=['shipped', 'closed_start'])
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     shipped = LmFst.read(os.path.join(ROOT, 'tests', 'golden', 'G_char_tg_syms.fst.gz'))
     res = {'date': datetime.date.today().isoformat(), 'device': torch.cuda.get_device_name(0),
            'frames': a.frames, 'steps': a.steps, 'beam': 10, 'lm': 'G_char_tg_syms.fst.gz',
-           'lm_weight': 0.75, 'coverage_weight': 0.8, 'coverage_tau': 0.25, 'configurations': {}}
+           'lm_weight': 0.75, 'coverage_weight': 0.8, 'coverage_tau': 0.25,
+           'force_forward': a.force_forward, 'learnable_initial_attention': not a.no_learnable_init,
+           'score_scale': a.score_scale, 'configurations': {}}
     for name, lm in (('shipped', shipped), ('closed_start', closed_start(shipped))):
-        res['configurations'][name] = run(a, dev, lm, name)
+        if name in a.configs:
+            res['configurations'][name] = run(a, dev, lm, name)
     if a.out:
         with open(a.out, 'w') as f:
             json.dump(res, f, indent=1)
