@@ -796,6 +796,82 @@ int asr_beam_lm_step_f32(const float *logits, const float *att, const int32_t *e
                          int32_t *parent, int32_t *frozen, int32_t *nsteps, void *stream);
 
 /*
+ * The graph search (GraphSearch, reference att_speech/modules/beam_search.py:406-648: BeamSearchLM
+ * that merges hypotheses whose recent history, LM-state set and attention agree) on the device;
+ * additions to ABI v24.  Per label step: asr_lm_label_costs_f64, asr_beam_lm_step_graph_f32,
+ * asr_lm_bag_advance_f64, asr_graph_merge_f32.
+ *
+ * asr_beam_lm_step_graph_f32: asr_beam_lm_step_f32 (the same kernel; every shared output bit for
+ * bit) with two more outputs.  fin_mask [hyps] int32: 1 where this step's finish test passed for
+ * that OLD beam slot, else 0; all 0 at step 0; left alone for frozen utterances.  tot_out [hyps]:
+ * the fused score (EOS ignored) of the chosen (beam, class) pair per NEW slot, with the same -inf
+ * padding rule as scores_out (the host's new_tot_scores).  tot_out is a buffer of its own.
+ *
+ * asr_graph_merge_f32: the two host loops of GraphSearch.step (reference :466-476 and :518-590),
+ * one workgroup of 256 threads per utterance, for the utterances with nsteps[b] == step + 1;
+ * launched after asr_lm_bag_advance_f64, because it reads the survivors' new bags.
+ * att [hyps, T] is this step's alignment as the step entry saw it (NOT re-indexed by parent),
+ * scores / tot [hyps] are scores_out / tot_out of the step entry (both modified), est_in / est_out
+ * the histories before / after the step, bag_state [hyps, bag_cap] / bag_n [hyps] the survivors'
+ * bags (both NULL: no LM term, the LM-state test is skipped and nodes carry an empty set),
+ * len_pow [Lcap + 1] fp32 with len_pow[l] = (float)(l ** length_normalization) filled by the host.
+ * The node store is the caller's, Ncap >= (step + 1) * beam nodes per utterance (every live slot of
+ * every step appends at most one node, so it cannot overflow; ASR_EINVAL otherwise), node index =
+ * insertion order: node_count [B] (init 0), node_score [B, Ncap] fp32, node_len [B, Ncap],
+ * node_tokens [B, Ncap, Lcap], node_att [B, Ncap, T] fp32, node_bag_n [B, Ncap], node_bag_state
+ * [B, Ncap, bag_cap], node_fin [B, Ncap], node_uplink [B, Ncap] (-1: none, else a node index of the
+ * same utterance).  Semantics, the host class's, quirks included:
+ *  - bucket: the nodes whose last `span` labels, left-filled with -1, are equal (span 0: one bucket
+ *    for all).  Labels are compared directly; collisions of Python's hash() between different
+ *    tuples, which would join buckets on the host, are not reproduced.
+ *  - finished marks come first: for every old slot with fin_mask set, every node whose label
+ *    sequence equals that slot's history in est_in (length step) gets fin = 1.
+ *  - the new slots are walked in order cur = 0 .. beam-1, each seeing what the earlier ones did
+ *    (appended nodes, uplinks, scores set to -inf); a slot whose scores[cur] is -inf is skipped and
+ *    appends nothing.
+ *  - candidates are the bucket's nodes in insertion order; one is skipped when it has an uplink,
+ *    when there is an LM term and its LM-state array differs from the slot's new bag states, or
+ *    when sum over t < enc_lens[b] of min(node_att[t], att[cur][t]) < merge_threshold.
+ *  - the alignment column is the one at the NEW slot index cur of this step's alignment, before
+ *    re-indexing by parent (the reference's att_weights[:, current_id]), not the parent's.
+ *  - score test in fp32: node_score / len_pow[node_len] >= tot[cur] / len_pow[step + 1].  True
+ *    (ties included), the old branch wins: scores[cur] = tot[cur] = -inf, the slot's uplink is that
+ *    candidate, the walk over candidates ends.  False, the new branch wins: the candidate's uplink
+ *    becomes the index the new node is about to get, every OTHER new slot whose history has the
+ *    candidate's sequence as a prefix gets -inf in both scores, and the walk goes on.
+ *  - then the node is appended: tot[cur] as it is now, the alignment column, the bag's states,
+ *    fin = 0, the history from est_out (length step + 1), the uplink.
+ *  - alias: the host stores a VIEW of new_tot_scores[cur], so when a later slot of the same step
+ *    drops slot cur, the node appended for cur in this step reads -inf from then on, also in the
+ *    score tests of that step.
+ *  - scores leaves the launch with the -inf entries (the host's self.scores = new_scores).
+ * No floating-point atomics; every sum has one owner and a fixed order (per-lane partial sums in
+ * frame order, then a fixed shuffle tree): launches are reproducible bit for bit.
+ * asr_graph_search_supported: beam <= 32, span >= 0, 1 <= T <= 8160, bag_cap == ASR_LM_BAG_CAP.
+ */
+int asr_graph_search_supported(int beam, int span, int T, int bag_cap);
+int asr_beam_lm_step_graph_f32(const float *logits, const float *att, const int32_t *enc_lens,
+                               const double *lm_cost, double lm_weight, const float *scores_in,
+                               float *scores_out, const int32_t *est_in, int32_t *est_out,
+                               const float *cov_in, float *cov_out, float *min_eos, int step, int B,
+                               int beam, int C, int T, int Lcap, float len_div,
+                               double min_attention_pos, float coverage_tau, float coverage_weight,
+                               int32_t *fin_count, int32_t *fin_parity, float *fin_score,
+                               int32_t *fin_len, int32_t *fin_beam, int32_t *fin_tokens,
+                               float *best_score, int32_t *best_len, int32_t *best_tokens,
+                               float *best_elems, int32_t *new_input, int32_t *parent,
+                               int32_t *frozen, int32_t *nsteps, int32_t *fin_mask, float *tot_out,
+                               void *stream);
+int asr_graph_merge_f32(const float *att, const int32_t *enc_lens, float *scores, float *tot,
+                        const int32_t *est_in, const int32_t *est_out, const int32_t *fin_mask,
+                        const int32_t *bag_state, const int32_t *bag_n, int bag_cap,
+                        const int32_t *nsteps, const float *len_pow, int step, int B, int beam, int T,
+                        int Lcap, int span, float merge_threshold, int Ncap, int32_t *node_count,
+                        float *node_score, int32_t *node_len, int32_t *node_tokens, float *node_att,
+                        int32_t *node_bag_n, int32_t *node_bag_state, int32_t *node_fin,
+                        int32_t *node_uplink, void *stream);
+
+/*
  * The step boundary on the device (ABI v18): the reference's GradientClipping hook
  * (att_speech/modules/hooks/gradient_clipping.py:13-53: clip_grad_norm_ to clip_norm, skip the
  * optimizer step when the unclipped norm exceeds skip_step_norm) and torch.optim.Adam.step

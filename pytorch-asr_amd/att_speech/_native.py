@@ -93,6 +93,10 @@ _SIGNATURES = {
     'asr_lm_bag_advance_f64': (_i, [_vp] * 6 + [_i, _i] + [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'asr_beam_lm_step_f32': (_i, [_vp, _vp, _vp, _vp, ctypes.c_double] + [_vp] * 7 + [_i] * 6 +
                              [_f, ctypes.c_double, _f, _f] + [_vp] * 15),
+    'asr_graph_search_supported': (_i, [_i, _i, _i, _i]),
+    'asr_beam_lm_step_graph_f32': (_i, [_vp, _vp, _vp, _vp, ctypes.c_double] + [_vp] * 7 + [_i] * 6 +
+                                   [_f, ctypes.c_double, _f, _f] + [_vp] * 17),
+    'asr_graph_merge_f32': (_i, [_vp] * 9 + [_i, _vp, _vp] + [_i] * 6 + [_f, _i] + [_vp] * 10),
     'asr_ctc_graph_build': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f] + [_vp] * 8),
     'asr_lattice_grouped_workspace_bytes': (_i64, [_i, _i, _i, _i]),
     'asr_lattice_grouped_fwbw_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i] + [_vp] * 8 +
@@ -1223,6 +1227,42 @@ def beam_lm_step(logits, att, lens, lm_cost, lm_weight, scores_in, scores_out, e
         _p(state['fin_beam']), _p(state['fin_tokens']), _p(state['best_score']), _p(state['best_len']),
         _p(state['best_tokens']), _p(state['best_elems']), _p(state['new_input']), _p(state['parent']),
         _p(state['frozen']), _p(state['nsteps']), _stream()), 'asr_beam_lm_step_f32')
+
+
+def graph_search_supported(beam, span, T, bag_cap=LM_BAG_CAP):
+    return bool(lib().asr_graph_search_supported(beam, span, T, bag_cap))
+
+
+def beam_lm_step_graph(logits, att, lens, lm_cost, lm_weight, scores_in, scores_out, est_in, est_out, cov_in,
+                       cov_out, min_eos, step, B, beam, len_div, min_attention_pos, coverage_tau,
+                       coverage_weight, state, fin_mask, tot_out):
+    """asr_beam_lm_step_graph_f32: beam_lm_step plus fin_mask [hyps] i32 and tot_out [hyps] f32."""
+    C, T = logits.shape[-1], att.shape[-1]
+    check(lib().asr_beam_lm_step_graph_f32(
+        _p(logits), _p(att), _p(lens), _p(lm_cost), float(lm_weight), _p(scores_in), _p(scores_out),
+        _p(est_in), _p(est_out), _p(cov_in), _p(cov_out), _p(min_eos), step, B, beam, C, T,
+        est_in.shape[1], len_div, float(min_attention_pos), coverage_tau, coverage_weight,
+        _p(state['fin_count']), _p(state['fin_parity']), _p(state['fin_score']), _p(state['fin_len']),
+        _p(state['fin_beam']), _p(state['fin_tokens']), _p(state['best_score']), _p(state['best_len']),
+        _p(state['best_tokens']), _p(state['best_elems']), _p(state['new_input']), _p(state['parent']),
+        _p(state['frozen']), _p(state['nsteps']), _p(fin_mask), _p(tot_out), _stream()),
+        'asr_beam_lm_step_graph_f32')
+
+
+NODE_KEYS = ('node_count', 'node_score', 'node_len', 'node_tokens', 'node_att', 'node_bag_n',
+             'node_bag_state', 'node_fin', 'node_uplink')
+
+
+def graph_merge(att, lens, scores, tot, est_in, est_out, fin_mask, bags, nsteps, len_pow, step, B, beam,
+                span, merge_threshold, store, bag_cap=LM_BAG_CAP):
+    """asr_graph_merge_f32: `bags` = (state [hyps, cap] i32, cost, n [hyps] i32) of the survivors or
+    None (no LM term); `store` = dict of the node arrays (NODE_KEYS) of include/asr_amd.h."""
+    T, Lcap, Ncap = att.shape[-1], est_in.shape[1], store['node_score'].shape[1]
+    check(lib().asr_graph_merge_f32(
+        _p(att), _p(lens), _p(scores), _p(tot), _p(est_in), _p(est_out), _p(fin_mask),
+        _p(bags[0]) if bags is not None else None, _p(bags[2]) if bags is not None else None, bag_cap,
+        _p(nsteps), _p(len_pow), step, B, beam, T, Lcap, int(span), float(merge_threshold), Ncap,
+        *([_p(store[k]) for k in NODE_KEYS] + [_stream()])), 'asr_graph_merge_f32')
 
 
 def beam_step(logits, scores_in, scores_out, est_in, est_out, step, B, beam, len_div, state):

@@ -9,6 +9,9 @@ by device-side gathers instead of the reference's Python `batch x beam` double
 loop (:108-124) and ONE host read-back per step for the finished-hypothesis
 bookkeeping instead of `.item()` calls inside loops (:58-81).
 
+DeviceBeamSearch, DeviceBeamSearchLM and DeviceGraphSearch keep all of their state on the device
+(include/asr_amd.h: asr_beam_step_f32; the launches of csrc/beam_lm.hip).
+
 Quirks kept on purpose (bit-compatible results):
   * `is_eos_best` is computed per hypothesis ([B*beam]) but indexed with the
     batch id (:73) — i.e. it looks at hypothesis `batch_id`, not at the batch's
@@ -426,36 +429,43 @@ class GraphSearch(BeamSearchLM):
     def get_graph(self):
         """(:598-648) vertices (hash, letter, score, coverage, finished) and edges
         (parent hash, hash, 'normal' | 'merged') per utterance."""
-        for hmap in self.graph:
-            for _, li in hmap.items():
-                for i in range(len(li)):
-                    if li[i][4] is not None:                     # follow uplinks to the sink
-                        t = i
-                        while li[t][4] is not None:
-                            t = li[t][4]
-                        li[i] = li[i][:4] + (t,)
-                for i in range(len(li)):
-                    li[i] = li[i][:5] + (hash(tuple(li[i][3].tolist())), li[i][3][-1])
-        G = []
-        for hmap in self.graph:
-            V = [(hash(()), '<sos>', 0.0, 0., False)]
-            valid = {hash(())}
-            E = []
-            for _, li in hmap.items():
-                for sc, atts, (fsts, fin, cov), ests, uplink, ests_hash, label in li:
-                    if uplink is None:
-                        valid.add(ests_hash)
-                        V.append((ests_hash, label.item(), sc.item(), cov, fin))
-            for _, li in hmap.items():
-                for sc, atts, (fsts, fin, cov), ests, uplink, ests_hash, label in li:
-                    parent = hash(tuple(ests[:-1].tolist()))
-                    me, kind = ests_hash, 'normal'
-                    if uplink is not None:
-                        me, kind = li[uplink][5], 'merged'
-                    if parent in valid and me in valid:
-                        E.append((parent, me, kind))
-            G.append({'V': V, 'E': E})
-        return G
+        return merge_graphs(self.graph)
+
+
+def merge_graphs(graph):
+    """GraphSearch.get_graph (:598-648) on `graph`, a list over the utterances of
+    {hist_hash: [(score, atts, (set_of_states, fin, cov), ests, uplink), ...]}: the one code
+    behind the host and the device class.  Uplinks are followed to their sinks in place."""
+    for hmap in graph:
+        for _, li in hmap.items():
+            for i in range(len(li)):
+                if li[i][4] is not None:                     # follow uplinks to the sink
+                    t = i
+                    while li[t][4] is not None:
+                        t = li[t][4]
+                    li[i] = li[i][:4] + (t,)
+            for i in range(len(li)):
+                li[i] = li[i][:5] + (hash(tuple(li[i][3].tolist())), li[i][3][-1])
+    G = []
+    for hmap in graph:
+        V = [(hash(()), '<sos>', 0.0, 0., False)]
+        valid = {hash(())}
+        E = []
+        for _, li in hmap.items():
+            for sc, atts, (fsts, fin, cov), ests, uplink, ests_hash, label in li:
+                if uplink is None:
+                    valid.add(ests_hash)
+                    V.append((ests_hash, label.item(), sc.item(), cov, fin))
+        for _, li in hmap.items():
+            for sc, atts, (fsts, fin, cov), ests, uplink, ests_hash, label in li:
+                parent = hash(tuple(ests[:-1].tolist()))
+                me, kind = ests_hash, 'normal'
+                if uplink is not None:
+                    me, kind = li[uplink][5], 'merged'
+                if parent in valid and me in valid:
+                    E.append((parent, me, kind))
+        G.append({'V': V, 'E': E})
+    return G
 
 
 class DeviceBeamSearch(object):
@@ -667,3 +677,109 @@ class DeviceBeamSearchLM(object):
         else:
             self.fst_states = [[] for _ in range(B)]
         return self
+
+
+# The node store of DeviceGraphSearch is refused above this many bytes (checked before anything
+# is allocated): the caller decodes on the host instead, one utterance at a time.
+GRAPH_STORE_BUDGET_BYTES = 2 << 30
+
+
+class DeviceGraphSearch(DeviceBeamSearchLM):
+    """GraphSearch (reference beam_search.py:406-648) on the MI355X for any number of utterances: B
+    utterances behave as B independent GraphSearch(batch_size=1) runs.  Per label step
+    `asr_lm_label_costs_f64`, `asr_beam_lm_step_graph_f32` (the BeamSearchLM step plus the finish
+    mask and the fused scores of the survivors), `asr_lm_bag_advance_f64` and `asr_graph_merge_f32`
+    (the merge bookkeeping on a per-utterance node store of max_steps * beam nodes, which every
+    step's slots fit by construction).  With beam 1 the merge launch is skipped and the graph
+    stays empty, as on the host.  `span` is the number of labels of the merge key (hash_dec's);
+    labels are compared directly, so collisions of Python's hash() between different keys are not
+    reproduced.  `finalize` rebuilds `self.graph` in the host's layout, a list over the utterances
+    of {hist_hash: [(score, atts, (set_of_states, fin, None), ests, uplink), ...]} with buckets
+    in insertion order and bucket-local uplinks; `get_graph` is the host's code."""
+
+    def __init__(self, hash_dec, merge_threshold, span, lm, lm_weight, alphabet_mapping,
+                 min_attention_pos, coverage_tau, coverage_weight, batch_size, beam_size, device,
+                 num_classes, length_normalization, max_steps, max_frames, enc_lens,
+                 keep_eos_score=False):
+        need = self.store_bytes(batch_size, beam_size, max_steps, max_frames)
+        if need > GRAPH_STORE_BUDGET_BYTES:
+            raise MemoryError('a node store of %d bytes is above the budget of %d'
+                              % (need, GRAPH_STORE_BUDGET_BYTES))
+        super(DeviceGraphSearch, self).__init__(
+            lm, lm_weight, alphabet_mapping, min_attention_pos, coverage_tau, coverage_weight,
+            batch_size, beam_size, device, num_classes, length_normalization, max_steps, max_frames,
+            enc_lens, keep_eos_score=keep_eos_score)
+        self.hash_dec, self.merge_threshold, self.span = hash_dec, float(merge_threshold), int(span)
+        B, beam, cap, T = batch_size, beam_size, max_steps + 1, max_frames
+        ncap, bc = max_steps * beam, self._native.LM_BAG_CAP
+        zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)  # noqa: E731
+        self._fin_mask = zi(B * beam)
+        self._tot = torch.zeros(B * beam, device=device)
+        self._len_pow = torch.tensor([float(l ** length_normalization) for l in range(cap + 1)],
+                                     dtype=torch.float32, device=device)
+        self._store = {
+            'node_count': zi(B), 'node_score': torch.zeros(B, ncap, device=device),
+            'node_len': zi(B, ncap), 'node_tokens': zi(B, ncap, cap),
+            'node_att': torch.zeros(B, ncap, T, device=device), 'node_bag_n': zi(B, ncap),
+            'node_bag_state': zi(B, ncap, bc), 'node_fin': zi(B, ncap),
+            'node_uplink': torch.full((B, ncap), -1, dtype=torch.int32, device=device)}
+        self.graph = [{} for _ in range(B)]
+
+    @staticmethod
+    def store_bytes(batch_size, beam_size, max_steps, max_frames):
+        from att_speech import _native
+        per_node = 4 * (5 + (max_steps + 1) + max_frames + _native.LM_BAG_CAP)
+        return batch_size * (4 + max_steps * beam_size * per_node)
+
+    def step(self, logits, att_weights, *args, **kwargs):
+        s, n, st = self._step, self._native, self._state
+        B, beam = self.batch_size, self.beam_size
+        assert (s + 1) * beam <= self._store['node_score'].shape[1]     # the store cannot overflow
+        logits = logits.reshape(-1, self.num_classes).contiguous()
+        att = att_weights.contiguous()
+        len_div = float(s ** self.length_normalization) if s > 0 else 1.0
+        i, o = s & 1, (s + 1) & 1
+        if self._use_lm:
+            n.lm_label_costs(self._lmdev, *self._bags[i], self._mapping, st['frozen'], B, beam,
+                             self.num_classes, self._cost)
+        n.beam_lm_step_graph(logits, att, self._lens, self._cost, self.lm_weight, self._scores[i],
+                             self._scores[o], self._est[i], self._est[o], self._cov[i], self._cov[o],
+                             self._min_eos, s, B, beam, len_div, self.min_attention_pos,
+                             self.coverage_tau, self.coverage_weight, st, self._fin_mask, self._tot)
+        if self._use_lm:
+            n.lm_bag_advance(self._lmdev, self._mapping, self._bags[i], self._bags[o], st['parent'],
+                             st['new_input'], st['nsteps'], s, B, beam, st['overflow'])
+        if beam > 1:
+            n.graph_merge(att, self._lens, self._scores[o], self._tot, self._est[i], self._est[o],
+                          self._fin_mask, self._bags[o] if self._use_lm else None, st['nsteps'],
+                          self._len_pow, s, B, beam, self.span, self.merge_threshold, self._store)
+        self._step = s + 1
+        return st['new_input'], st['parent']
+
+    def finalize(self):
+        super(DeviceGraphSearch, self).finalize()
+        store = {k: v.cpu() for k, v in self._store.items()}
+        lens = self._lens.cpu().tolist()
+        self.graph = []
+        for b in range(self.batch_size):
+            hmap, local, buckets = {}, [], []
+            for i in range(int(store['node_count'][b])):
+                ests = store['node_tokens'][b, i, :int(store['node_len'][b, i])].long()
+                nb = int(store['node_bag_n'][b, i])
+                li = hmap.setdefault(self.hash_dec(ests), [])
+                up = int(store['node_uplink'][b, i])
+                local.append(len(li))
+                buckets.append(li)
+                li.append((store['node_score'][b, i], store['node_att'][b, i, :lens[b]],
+                           (set(store['node_bag_state'][b, i, :nb].tolist()),
+                            bool(store['node_fin'][b, i]), None), ests, None if up < 0 else up))
+            # node indices -> bucket-local ones (an uplink may point at a node appended later)
+            for i, li in enumerate(buckets):
+                e = li[local[i]]
+                if e[4] is not None:
+                    li[local[i]] = e[:4] + (local[e[4]],)
+            self.graph.append(hmap)
+        return self
+
+    def get_graph(self):
+        return merge_graphs(self.graph)

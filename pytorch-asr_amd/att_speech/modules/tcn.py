@@ -482,11 +482,15 @@ class AttentionDecoderTCN(nn.Module):
         ASR_LM_BEAM_NATIVE, read per call: 0 keeps the host
         BeamSearchLM (one utterance at a time), 1 takes the device search for every batch size;
         unset, batches go to the device and a single utterance stays with the host class, which is
-        what it ran on before and against which the device search has not been timed yet."""
+        what it ran on before and against which the device search has not been timed yet.
+        A model with use_graph_search takes the device path (DeviceGraphSearch) only with
+        ASR_GRAPH_SEARCH_NATIVE=1, read per call, and then for every batch size, a single
+        utterance included, unless ASR_LM_BEAM_NATIVE=0."""
         switch = os.environ.get('ASR_LM_BEAM_NATIVE', '')
-        if switch == '0' or (switch != '1' and encoded.size(1) == 1):
+        graph_native = bool(self.use_graph_search) and self._native_graph_ok(encoded)
+        if switch == '0' or (switch != '1' and encoded.size(1) == 1 and not graph_native):
             return False
-        if self.rescore or self.use_graph_search or not self._native_window_ok():
+        if self.rescore or (self.use_graph_search and not graph_native) or not self._native_window_ok():
             return False
         if self.lm_weight == 0 and not self.coverage_weight > 0:
             return False
@@ -495,10 +499,24 @@ class AttentionDecoderTCN(nn.Module):
             return False
         return bool(encoded.is_cuda and lm.device_arrays(encoded.device) is not None)
 
+    def _graph_span(self):
+        """the number of labels in GraphSearch's merge key (hash_dec)"""
+        span = self.graph_search_history_len
+        return self.tcn.eff_history if span < 0 else span
+
+    def _native_graph_ok(self, encoded):
+        """ASR_GRAPH_SEARCH_NATIVE=1 (read per call; off by default) and shapes the merge kernel takes."""
+        if os.environ.get('ASR_GRAPH_SEARCH_NATIVE', '') != '1':
+            return False
+        from att_speech import _native
+        return _native.graph_search_supported(self.beam_size, self._graph_span(), encoded.size(0))
+
     def _decode_native(self, encoded, encoded_lens, return_attention, poll_every=8):
         """The MI355X decode loop, for the plain beam search and, with an LM, the LM-fused one
         (DeviceBeamSearchLM: asr_lm_label_costs_f64, asr_beam_lm_step_f32, asr_lm_bag_advance_f64 in
-        place of asr_beam_step_f32; None when an LM bag outgrew the cap): per label step the LM state of
+        place of asr_beam_step_f32; with use_graph_search and ASR_GRAPH_SEARCH_NATIVE=1 the graph search,
+        DeviceGraphSearch, which adds asr_graph_merge_f32; None when an LM bag outgrew the cap or the
+        graph search's node store its budget, `_native_gave_up` says which): per label step the LM state of
         the last frame as dense products (TCN.last_step), ONE launch for the local attention
         + context (asr_tcn_attention_step_f32, or asr_tcn_attention_step_win_f32 under a
         force_forward window), the output MLP, ONE launch for the beam
@@ -510,7 +528,20 @@ class AttentionDecoderTCN(nn.Module):
         beam, dev, attn = self.beam_size, encoded.device, self.attn
         hyps = B * beam
         lens = torch.as_tensor(encoded_lens).to(dev, torch.int32)
-        if self.lm:
+        self._native_gave_up = None
+        if self.lm and self.use_graph_search:
+            from att_speech.modules import beam_search as bs
+            need = bs.DeviceGraphSearch.store_bytes(B, beam, self.TRANSCRIPTION_LEN_GUARD, T)
+            if need > bs.GRAPH_STORE_BUDGET_BYTES:
+                self._native_gave_up = ('graph_store', need, bs.GRAPH_STORE_BUDGET_BYTES)
+                return None                              # refused before anything is allocated
+            search = bs.DeviceGraphSearch(
+                self.hash_dec, self.graph_search_merge_threshold, self._graph_span(),
+                self.lm, self.lm_weight, self.alphabet_mapping, self.min_attention_pos,
+                self.coverage_tau, self.coverage_weight, B, beam, dev, self.num_classes,
+                self.length_normalization, self.TRANSCRIPTION_LEN_GUARD, T, lens,
+                keep_eos_score=self.keep_eos_score)
+        elif self.lm:
             from att_speech.modules.beam_search import DeviceBeamSearchLM
             search = DeviceBeamSearchLM(
                 self.lm, self.lm_weight, self.alphabet_mapping, self.min_attention_pos,
@@ -554,20 +585,22 @@ class AttentionDecoderTCN(nn.Module):
         search.finalize()
         if getattr(search, 'overflow', 0):
             self._last_bag_overflow = search.overflow
+            self._native_gave_up = ('lm_bag_overflow', search.overflow, _native.LM_BAG_CAP)
             return None                                  # an LM bag outgrew the device's cap
         out = {'decoded': search.best_finished,
                'decoded_scores': search.best_finished_scores_elements,
                'loss': torch.Tensor(search.best_finished_scores).mean()}
         if return_attention:
             out.update(attweights=trace_att, logits=trace_logits)
-        out.update(coverage=search.coverage, graph=None, beam_search=search)
+        out.update(coverage=search.coverage, graph=search.get_graph(), beam_search=search)
         return out
 
     def _decode_host_each(self, encoded, encoded_lens, return_attention):
-        """The host BeamSearchLM takes one utterance per call: a batch whose device search gave up
-        (an LM bag above the cap) is decoded utterance by utterance, each on its own frames, and the
-        results are joined (lists over the utterances; `beam_search`, `coverage`, `attweights` and
-        `logits` are lists of the per-utterance values)."""
+        """The host BeamSearchLM / GraphSearch takes one utterance per call: a batch whose device
+        search gave up (an LM bag above the cap, a node store above the budget) is decoded utterance
+        by utterance, each on its own frames, and the results are joined (lists over the utterances;
+        `beam_search`, `coverage`, `attweights` and `logits` are lists of the per-utterance values,
+        `graph` of the per-utterance graphs for a graph-search model, None otherwise)."""
         lens = [int(v) for v in torch.as_tensor(encoded_lens).tolist()]
         old = os.environ.get('ASR_LM_BEAM_NATIVE')
         os.environ['ASR_LM_BEAM_NATIVE'] = '0'
@@ -586,7 +619,7 @@ class AttentionDecoderTCN(nn.Module):
         for k in ('attweights', 'logits', 'coverage', 'graph', 'beam_search'):
             if k in parts[0]:
                 out[k] = [p[k] for p in parts]
-        out['graph'] = None
+        out['graph'] = [p['graph'][0] for p in parts] if self.use_graph_search else None
         return out
 
     def decode(self, encoded, encoded_lens, texts=None, text_lens=None,
@@ -597,11 +630,17 @@ class AttentionDecoderTCN(nn.Module):
             if out is not None:
                 return out
             from att_speech import _native
-            if not _native._WARNED.get('lm_bag_overflow'):
-                _native._WARNED['lm_bag_overflow'] = True
-                warnings.warn('an LM bag of the device beam search asked for at least %d states, above '
-                              'its cap of %d: decoding this call with the host BeamSearchLM, one utterance at a time'
-                              % (self._last_bag_overflow, _native.LM_BAG_CAP))
+            why, asked, cap = self._native_gave_up
+            if not _native._WARNED.get(why):
+                _native._WARNED[why] = True
+                if why == 'graph_store':
+                    warnings.warn('the node store of the device graph search would take %d bytes, above its '
+                                  'budget of %d: decoding this call with the host GraphSearch, one utterance '
+                                  'at a time' % (asked, cap))
+                else:
+                    warnings.warn('an LM bag of the device beam search asked for at least %d states, above '
+                                  'its cap of %d: decoding this call with the host BeamSearchLM, one utterance at a time'
+                                  % (asked, cap))
             if encoded.size(1) > 1:
                 return self._decode_host_each(encoded, encoded_lens, return_attention)
         search = self._make_search(encoded.size(1), encoded.device)

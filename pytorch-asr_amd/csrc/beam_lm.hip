@@ -11,6 +11,10 @@
 //      this step's alignment, the sorted finished list, the best hypothesis and its score
 //      elements, the top-k on the fused score, the gather of the acoustic scores, the re-indexing
 //      of histories / coverage / EOS floors, and the per-utterance freeze.
+//  asr_beam_lm_step_graph_f32 — the same kernel with the two outputs GraphSearch.step needs on top:
+//      the finish mask of the old slots and the fused score of the chosen extensions.
+//  asr_graph_merge_f32 — the merge bookkeeping of GraphSearch.step (reference :466-476, :518-590)
+//      on a caller-owned node store, one workgroup per utterance, after the bags advanced.
 //  asr_lm_bag_advance_f64 — the bags of the survivors only: arcs of the chosen label out of the
 //      parent's bag (range search in the ilabel-sorted arcs), equal targets merged, then the
 //      epsilon closure level by level in eps_rank order.  One wave per survivor; lane i keeps
@@ -176,6 +180,8 @@ struct StepParams {
     int32_t *best_len, *best_tokens;
     float *best_elems;
     int32_t *new_input, *parent, *frozen, *nsteps;
+    int32_t *fin_mask;                       // graph entry only (NULL otherwise): [hyps]
+    float *tot_out;                          // graph entry only (NULL otherwise): [hyps]
 };
 
 constexpr int NT = 128;
@@ -190,7 +196,7 @@ __global__ __launch_bounds__(NT) void beam_lm_step_kernel(StepParams p) {
     __shared__ float m_score[2 * BEAM_MAX], o_score[BEAM_MAX];
     __shared__ int m_src[2 * BEAM_MAX], o_src[BEAM_MAX];
     __shared__ int s_ntot, s_nfin, s_added;
-    __shared__ float red_v[NT / 64], sel_v[BEAM_MAX];
+    __shared__ float red_v[NT / 64], sel_v[BEAM_MAX], sel_t[BEAM_MAX];
     __shared__ int red_i[NT / 64], sel_i[BEAM_MAX];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (p.frozen[b]) return;                 // its finished list was full after an earlier step
@@ -269,6 +275,7 @@ __global__ __launch_bounds__(NT) void beam_lm_step_kernel(StepParams p) {
                 c_nrm[k] = nrm;
                 // EOS strictly above every class (first maximum), the alignment far enough in
                 c_ok[k] = te > mo && (float)amax[k] > min_pos && (double)nrm > -1e10;
+                if (p.fin_mask) p.fin_mask[h0 + k] = c_ok[k];
             }
         }
         __syncthreads();
@@ -340,6 +347,8 @@ __global__ __launch_bounds__(NT) void beam_lm_step_kernel(StepParams p) {
                 s_nfin = nkeep;
             }
         }
+    } else if (p.fin_mask && tid < beam) {
+        p.fin_mask[h0 + tid] = 0;
     }
     __syncthreads();
 
@@ -390,6 +399,7 @@ __global__ __launch_bounds__(NT) void beam_lm_step_kernel(StepParams p) {
             else last = sel_i[r];
             const int it = sel_i[r];
             sel_v[r] = r >= pad_from ? -INFINITY : acoustic(it / Cm, it % Cm);   // acoustic only
+            if (p.tot_out) sel_t[r] = r >= pad_from ? -INFINITY : total(it / Cm, it % Cm);
         }
     }
     __syncthreads();
@@ -407,6 +417,7 @@ __global__ __launch_bounds__(NT) void beam_lm_step_kernel(StepParams p) {
         if (lane == 0) {
             dst[step] = letter;
             p.scores_out[hn] = sel_v[r];
+            if (p.tot_out) p.tot_out[hn] = sel_t[r];
             p.new_input[hn] = letter;
             p.parent[hn] = hp;
             if (p.min_eos) p.min_eos[hn] = eosl[kb];             // (all floors were read before the first barrier)
@@ -416,6 +427,180 @@ __global__ __launch_bounds__(NT) void beam_lm_step_kernel(StepParams p) {
         p.nsteps[b] = step + 1;
         if (s_nfin >= beam) p.frozen[b] = 1;
     }
+}
+
+// ------------------------------------------------------------------ graph search: hypothesis merging
+// GraphSearch.step's two host loops on the node store of one utterance per workgroup.  The walk
+// over the new slots is sequential (each sees what the earlier ones did); inside it the key /
+// uplink / LM-state filters run one thread per node, the matches are compacted in node order, one
+// wave per candidate takes the min-sum (per-lane partial sums in frame order, then the xor
+// tree), and wave 0 takes the decisions in candidate order with uniform control flow.  A node
+// appended in this launch reads its score from the slot it came from (the host stores a view of
+// new_tot_scores[cur]); the store is written back at the end.
+struct MergeParams {
+    const float *att;
+    const int32_t *lens;
+    float *scores, *tot;
+    const int32_t *est_in, *est_out, *fin_mask, *bag_state, *bag_n, *nsteps;
+    const float *len_pow;
+    int step, B, beam, T, Lcap, span, Ncap;
+    float thr;
+    int32_t *node_count;
+    float *node_score;
+    int32_t *node_len, *node_tokens;
+    float *node_att;
+    int32_t *node_bag_n, *node_bag_state, *node_fin, *node_uplink;
+};
+
+constexpr int MT = 256;
+constexpr int T_MAX = 8160;
+
+// the last `span` labels, left-filled with -1, agree (positions past both histories are fill)
+__device__ __forceinline__ bool key_equal(const int32_t *ta, int la, const int32_t *tb, int lb, int span) {
+    const int mx = la > lb ? la : lb;
+    const int n = span < mx ? span : mx;
+    for (int j = 1; j <= n; ++j) {
+        const int va = j <= la ? ta[la - j] : -1, vb = j <= lb ? tb[lb - j] : -1;
+        if (va != vb) return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(MT) void graph_merge_kernel(MergeParams p) {
+    __shared__ float s_ns[BEAM_MAX], s_nt[BEAM_MAX], s_sum[MT];
+    __shared__ int s_node[BEAM_MAX], s_slot[BEAM_MAX], s_cand[MT], s_wcnt[MT / 64];
+    __shared__ int s_count, s_break, s_up;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (p.nsteps[b] != p.step + 1) return;                  // frozen before this step
+    const int beam = p.beam, T = p.T, Lcap = p.Lcap, step = p.step, L = step + 1, Ncap = p.Ncap;
+    const int h0 = b * beam;
+    int len = p.lens[b];
+    len = len < 0 ? 0 : (len > T ? T : len);
+    float *nscore = p.node_score + (size_t)b * Ncap;
+    int32_t *nlen = p.node_len + (size_t)b * Ncap, *nfin = p.node_fin + (size_t)b * Ncap;
+    int32_t *nup = p.node_uplink + (size_t)b * Ncap, *nbagn = p.node_bag_n + (size_t)b * Ncap;
+    int32_t *ntok = p.node_tokens + (size_t)b * Ncap * Lcap;
+    int32_t *nbag = p.node_bag_state + (size_t)b * Ncap * CAP;
+    float *natt = p.node_att + (size_t)b * Ncap * T;
+    int count0 = p.node_count[b];
+    count0 = count0 < 0 ? 0 : (count0 > Ncap ? Ncap : count0);
+    if (tid < beam) {
+        s_ns[tid] = p.scores[h0 + tid];
+        s_nt[tid] = p.tot[h0 + tid];
+        s_node[tid] = -1;
+    }
+    if (tid == 0) s_count = count0;
+
+    // ---- finished marks first: the nodes that ARE the history of an old slot that finished ----
+    if (step > 0) {
+        for (int k = 0; k < beam; ++k) {
+            if (!p.fin_mask[h0 + k]) continue;
+            const int32_t *e = p.est_in + (size_t)(h0 + k) * Lcap;
+            for (int i = tid; i < count0; i += MT) {
+                if (nlen[i] != step) continue;
+                bool eq = true;
+                for (int j = 0; j < step && eq; ++j) eq = ntok[(size_t)i * Lcap + j] == e[j];
+                if (eq) nfin[i] = 1;
+            }
+        }
+    }
+    volatile float *vns = s_ns, *vnt = s_nt;
+
+    // ---- the new slots in order ----------------------------------------------------------------
+    for (int cur = 0; cur < beam; ++cur) {
+        __syncthreads();
+        if (vns[cur] == -INFINITY) continue;                 // a dropped slot appends nothing
+        const int cnt = s_count;
+        const int32_t *e = p.est_out + (size_t)(h0 + cur) * Lcap;
+        // (the column at the NEW slot index of this step's alignment, not the parent's: the quirk)
+        const float *a = p.att + (size_t)(h0 + cur) * T;
+        int bn = 0;
+        const int32_t *bs = nullptr;
+        if (p.bag_state) {
+            bn = p.bag_n[h0 + cur];
+            bn = bn < 0 ? 0 : (bn > CAP ? CAP : bn);
+            bs = p.bag_state + (size_t)(h0 + cur) * CAP;
+        }
+        if (tid == 0) { s_break = 0; s_up = -1; }
+        for (int base = 0; base < cnt; base += MT) {
+            __syncthreads();
+            if (s_break) break;
+            const int i = base + tid;
+            bool pass = false;
+            if (i < cnt && nup[i] < 0) {                     // a node with an uplink is dead
+                int nl = nlen[i];
+                nl = nl < 0 ? 0 : (nl > Lcap ? Lcap : nl);
+                pass = key_equal(ntok + (size_t)i * Lcap, nl, e, L, p.span);
+                if (pass && bs) {                            // the LM-state sets, as sorted arrays
+                    pass = nbagn[i] == bn;
+                    for (int j = 0; j < bn && pass; ++j) pass = nbag[(size_t)i * CAP + j] == bs[j];
+                }
+            }
+            const unsigned long long m = __ballot(pass);
+            if (lane == 0) s_wcnt[wave] = __popcll(m);
+            __syncthreads();
+            int off = 0, ncand = 0;
+            for (int w = 0; w < MT / 64; ++w) {
+                if (w < wave) off += s_wcnt[w];
+                ncand += s_wcnt[w];
+            }
+            if (ncand == 0) continue;
+            if (pass) s_cand[off + __popcll(m & ((1ull << lane) - 1ull))] = i;
+            __syncthreads();
+            for (int c = wave; c < ncand; c += MT / 64) {
+                const float *na = natt + (size_t)s_cand[c] * T;
+                float s = 0.f;
+                for (int t = lane; t < len; t += 64) s += fminf(na[t], a[t]);
+                s = wave_sum(s);
+                if (lane == 0) s_sum[c] = s;
+            }
+            __syncthreads();
+            if (wave == 0) {
+                const float mine = vnt[cur] / p.len_pow[L];
+                for (int c = 0; c < ncand; ++c) {
+                    if (s_sum[c] < p.thr) continue;          // a different branch
+                    const int i = s_cand[c];
+                    int nl = nlen[i];
+                    nl = nl < 0 ? 0 : (nl > Lcap ? Lcap : nl);
+                    const float old = i >= count0 ? vnt[s_slot[i - count0]] : nscore[i];
+                    if (old / p.len_pow[nl] >= mine) {       // the old branch is better (ties too)
+                        if (lane == 0) { vns[cur] = -INFINITY; vnt[cur] = -INFINITY; s_up = i; s_break = 1; }
+                        break;
+                    }
+                    if (lane == 0) nup[i] = cnt;             // the index the new node is about to get
+                    if (lane < beam && lane != cur) {        // drop the candidate's descendants
+                        const int32_t *ct = ntok + (size_t)i * Lcap;
+                        const int32_t *o = p.est_out + (size_t)(h0 + lane) * Lcap;
+                        bool pre = nl <= L;
+                        for (int j = 0; j < nl && pre; ++j) pre = ct[j] == o[j];
+                        if (pre) { vns[lane] = -INFINITY; vnt[lane] = -INFINITY; }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (cnt < Ncap) {                                    // (cannot fail: Ncap >= (step + 1) * beam)
+            for (int j = tid; j < L; j += MT) ntok[(size_t)cnt * Lcap + j] = e[j];
+            for (int t = tid; t < T; t += MT) natt[(size_t)cnt * T + t] = a[t];
+            for (int j = tid; j < bn; j += MT) nbag[(size_t)cnt * CAP + j] = bs[j];
+            if (tid == 0) {
+                nlen[cnt] = L;
+                nbagn[cnt] = bn;
+                nfin[cnt] = 0;
+                nup[cnt] = s_up;
+                s_node[cur] = cnt;
+                s_slot[cnt - count0] = cur;
+                s_count = cnt + 1;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < beam) {
+        p.scores[h0 + tid] = s_ns[tid];
+        p.tot[h0 + tid] = s_nt[tid];
+        if (s_node[tid] >= 0) nscore[s_node[tid]] = s_nt[tid];   // the view: later drops show
+    }
+    if (tid == 0) p.node_count[b] = s_count;
 }
 
 }  // namespace
@@ -468,7 +653,7 @@ extern "C" int asr_lm_bag_advance_f64(const int32_t *ptr, const int32_t *ptr_ne,
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
 }
 
-extern "C" int asr_beam_lm_step_f32(const float *logits, const float *att, const int32_t *enc_lens,
+static int beam_lm_step_launch(const float *logits, const float *att, const int32_t *enc_lens,
                                     const double *lm_cost, double lm_weight,
                                     const float *scores_in, float *scores_out,
                                     const int32_t *est_in, int32_t *est_out,
@@ -479,7 +664,8 @@ extern "C" int asr_beam_lm_step_f32(const float *logits, const float *att, const
                                     int32_t *fin_len, int32_t *fin_beam, int32_t *fin_tokens,
                                     float *best_score, int32_t *best_len, int32_t *best_tokens,
                                     float *best_elems, int32_t *new_input, int32_t *parent,
-                                    int32_t *frozen, int32_t *nsteps, void *stream) {
+                                    int32_t *frozen, int32_t *nsteps, int32_t *fin_mask, float *tot_out,
+                                    void *stream) {
     if (B <= 0 || beam <= 0 || C < 2 || T <= 0 || step < 0 || Lcap <= step) return ASR_EINVAL;
     if (!asr_beam_lm_supported(beam, C, CAP)) return ASR_EUNSUPPORTED;
     if (!logits || !att || !enc_lens || !scores_in || !scores_out || !est_in || !est_out || !fin_count ||
@@ -498,7 +684,81 @@ extern "C" int asr_beam_lm_step_f32(const float *logits, const float *att, const
     p.fin_count = fin_count; p.fin_par = fin_parity; p.fin_score = fin_score; p.fin_len = fin_len;
     p.fin_beam = fin_beam; p.fin_tokens = fin_tokens; p.best_score = best_score; p.best_len = best_len;
     p.best_tokens = best_tokens; p.best_elems = best_elems; p.new_input = new_input; p.parent = parent;
-    p.frozen = frozen; p.nsteps = nsteps;
+    p.frozen = frozen; p.nsteps = nsteps; p.fin_mask = fin_mask; p.tot_out = tot_out;
     hipLaunchKernelGGL(beam_lm_step_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+}
+
+extern "C" int asr_beam_lm_step_f32(const float *logits, const float *att, const int32_t *enc_lens,
+                                    const double *lm_cost, double lm_weight,
+                                    const float *scores_in, float *scores_out,
+                                    const int32_t *est_in, int32_t *est_out,
+                                    const float *cov_in, float *cov_out, float *min_eos,
+                                    int step, int B, int beam, int C, int T, int Lcap, float len_div,
+                                    double min_attention_pos, float coverage_tau, float coverage_weight,
+                                    int32_t *fin_count, int32_t *fin_parity, float *fin_score,
+                                    int32_t *fin_len, int32_t *fin_beam, int32_t *fin_tokens,
+                                    float *best_score, int32_t *best_len, int32_t *best_tokens,
+                                    float *best_elems, int32_t *new_input, int32_t *parent,
+                                    int32_t *frozen, int32_t *nsteps, void *stream) {
+    return beam_lm_step_launch(logits, att, enc_lens, lm_cost, lm_weight, scores_in, scores_out, est_in, est_out,
+                              cov_in, cov_out, min_eos, step, B, beam, C, T, Lcap, len_div, min_attention_pos,
+                              coverage_tau, coverage_weight, fin_count, fin_parity, fin_score, fin_len, fin_beam,
+                              fin_tokens, best_score, best_len, best_tokens, best_elems, new_input, parent, frozen,
+                              nsteps, nullptr, nullptr, stream);
+}
+
+extern "C" int asr_beam_lm_step_graph_f32(const float *logits, const float *att, const int32_t *enc_lens,
+                                    const double *lm_cost, double lm_weight,
+                                    const float *scores_in, float *scores_out,
+                                    const int32_t *est_in, int32_t *est_out,
+                                    const float *cov_in, float *cov_out, float *min_eos,
+                                    int step, int B, int beam, int C, int T, int Lcap, float len_div,
+                                    double min_attention_pos, float coverage_tau, float coverage_weight,
+                                    int32_t *fin_count, int32_t *fin_parity, float *fin_score,
+                                    int32_t *fin_len, int32_t *fin_beam, int32_t *fin_tokens,
+                                    float *best_score, int32_t *best_len, int32_t *best_tokens,
+                                    float *best_elems, int32_t *new_input, int32_t *parent,
+                                    int32_t *frozen, int32_t *nsteps, int32_t *fin_mask, float *tot_out,
+                                    void *stream) {
+    if (!fin_mask || !tot_out || tot_out == scores_out || tot_out == scores_in) return ASR_EINVAL;
+    return beam_lm_step_launch(logits, att, enc_lens, lm_cost, lm_weight, scores_in, scores_out, est_in, est_out,
+                              cov_in, cov_out, min_eos, step, B, beam, C, T, Lcap, len_div, min_attention_pos,
+                              coverage_tau, coverage_weight, fin_count, fin_parity, fin_score, fin_len, fin_beam,
+                              fin_tokens, best_score, best_len, best_tokens, best_elems, new_input, parent, frozen,
+                              nsteps, fin_mask, tot_out, stream);
+}
+
+extern "C" int asr_graph_search_supported(int beam, int span, int T, int bag_cap) {
+    return beam >= 1 && beam <= BEAM_MAX && span >= 0 && T >= 1 && T <= T_MAX && bag_cap == CAP;
+}
+
+extern "C" int asr_graph_merge_f32(const float *att, const int32_t *enc_lens, float *scores, float *tot,
+                                   const int32_t *est_in, const int32_t *est_out, const int32_t *fin_mask,
+                                   const int32_t *bag_state, const int32_t *bag_n, int bag_cap,
+                                   const int32_t *nsteps, const float *len_pow, int step, int B, int beam,
+                                   int T, int Lcap, int span, float merge_threshold, int Ncap,
+                                   int32_t *node_count, float *node_score, int32_t *node_len,
+                                   int32_t *node_tokens, float *node_att, int32_t *node_bag_n,
+                                   int32_t *node_bag_state, int32_t *node_fin, int32_t *node_uplink,
+                                   void *stream) {
+    if (B <= 0 || beam <= 0 || T <= 0 || step < 0 || Lcap <= step || span < 0 || Ncap <= 0) return ASR_EINVAL;
+    if (!asr_graph_search_supported(beam, span, T, bag_cap)) return ASR_EUNSUPPORTED;
+    if (!att || !enc_lens || !scores || !tot || !est_in || !est_out || !fin_mask || !nsteps || !len_pow ||
+        !node_count || !node_score || !node_len || !node_tokens || !node_att || !node_bag_n ||
+        !node_bag_state || !node_fin || !node_uplink)
+        return ASR_EINVAL;
+    if ((bag_state == nullptr) != (bag_n == nullptr) || scores == tot || est_in == est_out) return ASR_EINVAL;
+    if (!(merge_threshold == merge_threshold)) return ASR_EINVAL;
+    if ((long)(step + 1) * beam > (long)Ncap) return ASR_EINVAL;   // the store holds every step's slots
+    MergeParams p;
+    p.att = att; p.lens = enc_lens; p.scores = scores; p.tot = tot; p.est_in = est_in; p.est_out = est_out;
+    p.fin_mask = fin_mask; p.bag_state = bag_state; p.bag_n = bag_n; p.nsteps = nsteps; p.len_pow = len_pow;
+    p.step = step; p.B = B; p.beam = beam; p.T = T; p.Lcap = Lcap; p.span = span; p.Ncap = Ncap;
+    p.thr = merge_threshold;
+    p.node_count = node_count; p.node_score = node_score; p.node_len = node_len; p.node_tokens = node_tokens;
+    p.node_att = node_att; p.node_bag_n = node_bag_n; p.node_bag_state = node_bag_state;
+    p.node_fin = node_fin; p.node_uplink = node_uplink;
+    hipLaunchKernelGGL(graph_merge_kernel, dim3(B), dim3(MT), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
 }

@@ -23,7 +23,14 @@ the spread over the timed calls and, with --out, writes them as JSON.
 reference's readme does; --score-scale X draws the attention's score vector (zero at
 initialisation: uniform, hence diffuse alignments and an inactive window) from N(0, X^2 / A), and
 the fraction of (step, hypothesis) rows with an active window is reported.  --configs selects
-among `shipped` and `closed_start`."""
+among `shipped` and `closed_start`.
+
+--graph measures the graph search instead (use_graph_search, the lattice generation of the
+reference's readme) with the readme recipe's settings: window (-10, 50), beam 10, lm_weight 0.75,
+coverage 0.8 / 0.25, length_normalization 0, merge threshold 0.8, the `closed_start` LM, 334 frames
+unless --frames is given.  Device path (DeviceGraphSearch, ASR_GRAPH_SEARCH_NATIVE=1) at B in
+--batches (default 1 16 64) against the host GraphSearch looped over single utterances with the
+switch unset; nodes and merged nodes per utterance are reported beside the rates."""
 import argparse
 import datetime
 import json
@@ -116,6 +123,59 @@ def run(a, dev, lm, name):
     return res
 
 
+def run_graph(a, dev, lm):
+    vocab = lm_vocabulary(lm)
+    torch.manual_seed(0)
+    dec = AttentionDecoderTCN(
+        {'features': torch.zeros(a.frames, 2, a.encoded)}, len(vocab), tcn_hidden_size=384,
+        att_hidden_size=64, dropout_p=0.3, kernel_size=3, dilation_sizes=[1, 2], tcn_layers_per_block=2,
+        beam_size=10, length_normalization=0, vocabulary=vocab, lm_file=lm, lm_weight=0.75,
+        coverage_weight=0.8, coverage_tau=0.25, min_attention_pos=2.0, att_force_forward=(-10, 50),
+        use_graph_search=True, graph_search_merge_threshold=0.8,
+        learnable_initial_attention=not a.no_learnable_init).eval()
+    if a.score_scale > 0:
+        with torch.no_grad():
+            dec.attn.hidden_to_score.weight.normal_(0.0, a.score_scale / 64 ** 0.5)
+    dec = dec.to(dev)
+    dec.TRANSCRIPTION_LEN_GUARD = a.steps
+    bmax = max(a.batches)
+    enc = torch.randn(a.frames, bmax, a.encoded, generator=torch.Generator().manual_seed(1)).to(dev)
+    res = {'device_path': {}, 'host_path': {}, 'merge_key_labels': dec._graph_span()}
+
+    def stats(ups, **kw):
+        ups = sorted(ups)
+        return dict(utt_per_s_median=ups[len(ups) // 2], utt_per_s_min=ups[0], utt_per_s_max=ups[-1],
+                    calls=len(ups), **kw)
+    with torch.no_grad():
+        os.environ['ASR_GRAPH_SEARCH_NATIVE'] = '1'
+        for B in a.batches:
+            e, lens = enc[:, :B].contiguous(), torch.full((B,), a.frames)
+            out = dec.decode(e, lens)
+            kind = type(out['beam_search']).__name__
+            assert kind == 'DeviceGraphSearch', kind
+            store = out['beam_search']._store
+            nodes = float(store['node_count'].float().mean())
+            merged = float((store['node_uplink'] >= 0).sum()) / B
+            st = stats([B / t for t in timed(lambda: dec.decode(e, lens), a.iters)], search=kind,
+                       nodes_per_utt=nodes, merged_per_utt=merged)
+            res['device_path'][str(B)] = st
+            print('graph %-18s B=%-4d %.2f utt/s (min %.2f max %.2f over %d calls; %.0f nodes, %.0f merged per utterance)'
+                  % (kind, B, st['utt_per_s_median'], st['utt_per_s_min'], st['utt_per_s_max'], st['calls'],
+                     nodes, merged), flush=True)
+        del os.environ['ASR_GRAPH_SEARCH_NATIVE']
+        n = min(a.host_utts, bmax)
+
+        def host():
+            for b in range(n):
+                o = dec.decode(enc[:, b:b + 1].contiguous(), torch.tensor([a.frames]))
+            assert type(o['beam_search']).__name__ == 'GraphSearch'
+        st = stats([n / t for t in timed(host, max(1, a.iters - 1))], utterances_per_call=n)
+        res['host_path']['1'] = st
+        print('graph host GraphSearch    B=1    %.2f utt/s (min %.2f max %.2f over %d calls of %d utterances)' % (
+            st['utt_per_s_median'], st['utt_per_s_min'], st['utt_per_s_max'], st['calls'], n), flush=True)
+    return res
+
+
 def timed(fn, n):
     fn()
     torch.cuda.synchronize()
@@ -130,8 +190,9 @@ def timed(fn, n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--batches', type=int, nargs='+', default=[1, 16, 256])
-    ap.add_argument('--frames', type=int, default=125)
+    ap.add_argument('--graph', action='store_true')
+    ap.add_argument('--batches', type=int, nargs='+', default=None)
+    ap.add_argument('--frames', type=int, default=None)
     ap.add_argument('--encoded', type=int, default=320)
     ap.add_argument('--steps', type=int, default=250)
     ap.add_argument('--iters', type=int, default=3)
@@ -142,6 +203,10 @@ def main():
     ap.add_argument('--score-scale', type=float, default=0.0)
     ap.add_argument('--configs', nargs='+', default=['shipped', 'closed_start'])
     a = ap.parse_args()
+    if a.batches is None:
+        a.batches = [1, 16, 64] if a.graph else [1, 16, 256]
+    if a.frames is None:
+        a.frames = 334 if a.graph else 125
     dev = torch.device('cuda:0')
     shipped = LmFst.read(os.path.join(ROOT, 'tests', 'golden', 'G_char_tg_syms.fst.gz'))
     res = {'date': datetime.date.today().isoformat(), 'device': torch.cuda.get_device_name(0),
@@ -149,8 +214,12 @@ def main():
            'lm_weight': 0.75, 'coverage_weight': 0.8, 'coverage_tau': 0.25,
            'force_forward': a.force_forward, 'learnable_initial_attention': not a.no_learnable_init,
            'score_scale': a.score_scale, 'configurations': {}}
+    if a.graph:
+        res.update(beam=10, length_normalization=0, merge_threshold=0.8, force_forward=[-10, 50],
+                   use_graph_search=True)
+        res['configurations']['closed_start'] = run_graph(a, dev, closed_start(shipped))
     for name, lm in (('shipped', shipped), ('closed_start', closed_start(shipped))):
-        if name in a.configs:
+        if name in a.configs and not a.graph:
             res['configurations'][name] = run(a, dev, lm, name)
     if a.out:
         with open(a.out, 'w') as f:
