@@ -872,6 +872,44 @@ int asr_graph_merge_f32(const float *att, const int32_t *enc_lens, float *scores
                         int32_t *node_uplink, void *stream);
 
 /*
+ * Forced scoring of given sentences through their prefix trie (the teacher-forced pass of the
+ * reference's egs/wsj/local/lattice_search/rescore_lattices2.py and score_groundtruth.py,
+ * score_acoustic); an addition to ABI v24.  The sentences of an utterance, EOS appended, form a
+ * trie; the distinct prefixes of length l are the UNITS of level l, and one level is one label step
+ * of the decoder for all of them (asr_tcn_attention_step_f32 with parent = the unit extended).
+ *
+ * asr_forced_level_f32: the bookkeeping of one trie level, one workgroup of 256 threads per unit
+ * slot, no read-back.  B utterances with `width` slots each: slot p belongs to utterance p / width.
+ * logits [B * width, C] (class C-1 = EOS) and att [B * width, T] are this step's outputs per slot.
+ *  - cov_out[p, t] = cov_in[parent[p], t] + att[p, t] for t < T (one fp32 add).  cov_in has
+ *    cov_in_rows rows (the previous level's slots; at level 0 the initial alignments, which the
+ *    reference's coverage includes) and parent [B * width] indexes them; cov_in and cov_out are
+ *    distinct buffers that the caller alternates.
+ *  - The outgoing edges of slot p are edge_ptr[p] .. edge_ptr[p + 1] (edge_ptr [B * width + 1],
+ *    ascending, <= n_edges) of edge_label / edge_dst [n_edges].  With m = max_c logits[p, c] and
+ *    ls = log sum_c exp(logits[p, c] - m), edge e carries
+ *        v = acoustic_in[p] + (double)((logits[p, edge_label[e]] - m) - ls):
+ *    fp32 terms (log_softmax(logits)[label]) in an fp64 running sum, the reference's sum() of .item()
+ *    values.  edge_dst[e] >= 0: a slot of the NEXT level, acoustic_out[edge_dst[e]] = v
+ *    (acoustic_out [n_out]; acoustic_in [B * width] is all 0 at level 0; distinct buffers).
+ *    edge_dst[e] < 0: the EOS edge of sentence s = -1 - edge_dst[e] (< n_sent), sent_acoustic[s] = v
+ *    and sent_covered[s] = #{t < enc_lens[p / width] : cov_out[p, t] > coverage_tau} (int32, counted
+ *    once per slot).  Every destination has exactly one edge in the whole trie.
+ *  - A slot without edges (edge_ptr[p] == edge_ptr[p + 1]) is dead: it writes its cov_out row and
+ *    nothing else.  Edges whose label, destination or sentence is out of range are skipped.
+ * The class sum runs per lane over c = lane, lane + 64, ... and through the xor-shuffle tree, the
+ * count per thread over t = tid, tid + 256, ..., the tree, then waves 0..3: launches are
+ * reproducible bit for bit, there is no atomic.  Limits (the step kernel's): 2 <= C <= 2048,
+ * 1 <= T <= 8160, ASR_EUNSUPPORTED beyond; NULL or aliased buffers ASR_EINVAL, before any launch.
+ */
+int asr_forced_level_f32(const float *logits, const float *att, const float *cov_in, float *cov_out,
+                         const int32_t *parent, const int32_t *edge_ptr, const int32_t *edge_label,
+                         const int32_t *edge_dst, const double *acoustic_in, double *acoustic_out,
+                         const int32_t *enc_lens, int B, int width, int C, int T, int cov_in_rows,
+                         int n_edges, int n_out, int n_sent, float coverage_tau,
+                         double *sent_acoustic, int32_t *sent_covered, void *stream);
+
+/*
  * The step boundary on the device (ABI v18): the reference's GradientClipping hook
  * (att_speech/modules/hooks/gradient_clipping.py:13-53: clip_grad_norm_ to clip_norm, skip the
  * optimizer step when the unclipped norm exceeds skip_step_norm) and torch.optim.Adam.step

@@ -97,6 +97,7 @@ _SIGNATURES = {
     'asr_beam_lm_step_graph_f32': (_i, [_vp, _vp, _vp, _vp, ctypes.c_double] + [_vp] * 7 + [_i] * 6 +
                                    [_f, ctypes.c_double, _f, _f] + [_vp] * 17),
     'asr_graph_merge_f32': (_i, [_vp] * 9 + [_i, _vp, _vp] + [_i] * 6 + [_f, _i] + [_vp] * 10),
+    'asr_forced_level_f32': (_i, [_vp] * 11 + [_i] * 8 + [_f, _vp, _vp, _vp]),
     'asr_ctc_graph_build': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f] + [_vp] * 8),
     'asr_lattice_grouped_workspace_bytes': (_i64, [_i, _i, _i, _i]),
     'asr_lattice_grouped_fwbw_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i] + [_vp] * 8 +
@@ -1263,6 +1264,29 @@ def graph_merge(att, lens, scores, tot, est_in, est_out, fin_mask, bags, nsteps,
         _p(bags[0]) if bags is not None else None, _p(bags[2]) if bags is not None else None, bag_cap,
         _p(nsteps), _p(len_pow), step, B, beam, T, Lcap, int(span), float(merge_threshold), Ncap,
         *([_p(store[k]) for k in NODE_KEYS] + [_stream()])), 'asr_graph_merge_f32')
+
+
+def forced_level(logits, att, cov_in, cov_out, parent, edge_ptr, edge_label, edge_dst, acoustic_in,
+                 acoustic_out, lens, B, width, coverage_tau, sent_acoustic, sent_covered):
+    """asr_forced_level_f32: one trie level of the forced scorer.  logits [B*width, C], att / cov_out
+    [B*width, T], cov_in [rows, T] indexed by parent [B*width]; edges in CSR form per slot; fp64
+    acoustic carries; sent_acoustic fp64 / sent_covered i32 per sentence."""
+    slots = B * width
+    C, T = logits.shape[-1], att.shape[-1]
+    assert logits.shape[0] == slots and att.shape[0] == slots and cov_out.shape[0] >= slots
+    assert cov_in.shape[-1] == T and cov_out.shape[-1] == T and parent.numel() >= slots
+    assert edge_ptr.numel() >= slots + 1 and acoustic_in.numel() >= slots
+    assert edge_dst.numel() == edge_label.numel() and sent_covered.numel() == sent_acoustic.numel()
+    check(lib().asr_forced_level_f32(
+        _p(_dev(logits, torch.float32, 'logits')), _p(_dev(att, torch.float32, 'att')),
+        _p(_dev(cov_in, torch.float32, 'cov_in')), _p(_dev(cov_out, torch.float32, 'cov_out')),
+        _p(_dev(parent, torch.int32, 'parent')), _p(_dev(edge_ptr, torch.int32, 'edge_ptr')),
+        _p(_dev(edge_label, torch.int32, 'edge_label')), _p(_dev(edge_dst, torch.int32, 'edge_dst')),
+        _p(_dev(acoustic_in, torch.float64, 'acoustic_in')),
+        _p(_dev(acoustic_out, torch.float64, 'acoustic_out')), _p(_dev(lens, torch.int32, 'lens')),
+        B, width, C, T, cov_in.shape[0], edge_label.numel(), acoustic_out.numel(),
+        sent_acoustic.numel(), float(coverage_tau), _p(_dev(sent_acoustic, torch.float64, 'sent_acoustic')),
+        _p(_dev(sent_covered, torch.int32, 'sent_covered')), _stream()), 'asr_forced_level_f32')
 
 
 def beam_step(logits, scores_in, scores_out, est_in, est_out, step, B, beam, len_div, state):

@@ -10,7 +10,9 @@ loop (:108-124) and ONE host read-back per step for the finished-hypothesis
 bookkeeping instead of `.item()` calls inside loops (:58-81).
 
 DeviceBeamSearch, DeviceBeamSearchLM and DeviceGraphSearch keep all of their state on the device
-(include/asr_amd.h: asr_beam_step_f32; the launches of csrc/beam_lm.hip).
+(include/asr_amd.h: asr_beam_step_f32; the launches of csrc/beam_lm.hip).  `graph_sentences`,
+`sentence_trie` and DeviceForcedScorer (asr_forced_level_f32, csrc/forced_score.hip) serve
+`AttentionDecoderTCN.score_sentences`, the forced rescoring of a lattice's sentences.
 
 Quirks kept on purpose (bit-compatible results):
   * `is_eos_best` is computed per hypothesis ([B*beam]) but indexed with the
@@ -783,3 +785,251 @@ class DeviceGraphSearch(DeviceBeamSearchLM):
 
     def get_graph(self):
         return merge_graphs(self.graph)
+
+
+# ---------------------------------------------------------------------------------------------
+# Forced scoring of given sentences (the reference's egs/wsj/local/lattice_search scripts)
+# ---------------------------------------------------------------------------------------------
+def graph_sentences(graph, limit=None):
+    """The label-id sentences of every path from the root to a finished node of `graph`, one
+    {'V': [(hash, label, score, coverage, finished), ...], 'E': [(parent, child, kind), ...]} as
+    `decode` returns per utterance (get_graph / merge_graphs; V[0] is the root): the `dfs` of
+    rescore_lattices2.py, iteratively and over label ids instead of characters.  A node's sentence
+    comes before those of its children, children in edge order; a node reached along several paths
+    yields one sentence per path.  Stops after `limit` sentences.  An edge back to a node of the
+    current path is not followed (the script's recursion would not end on it)."""
+    if limit is not None and limit <= 0:
+        return []
+    nodes = {v[0]: v for v in graph['V']}               # a repeated hash keeps its last entry
+    children = {h: [] for h in nodes}
+    for edge in graph['E']:
+        children[edge[0]].append(edge[1])
+    root = graph['V'][0][0]
+    out, path, on_path = [], [], {root}
+    if nodes[root][4]:
+        out.append([])
+    stack = [(root, iter(children[root]))]
+    while stack and (limit is None or len(out) < limit):
+        node, it = stack[-1]
+        nxt = next(it, None)
+        if nxt is None:
+            stack.pop()
+            on_path.discard(node)
+            if path:
+                path.pop()
+            continue
+        if nxt in on_path:
+            continue
+        path.append(int(nodes[nxt][1]))
+        on_path.add(nxt)
+        if nodes[nxt][4]:
+            out.append(list(path))
+        stack.append((nxt, iter(children[nxt])))
+    return out
+
+
+def sentence_trie(sentences, eos):
+    """The prefix trie of one utterance's sentences (lists of labels, no EOS), level by level.
+    Returns {'inverse': distinct-sentence id of every given sentence, 'count': number of distinct
+    sentences, 'lengths': their lengths (without EOS), 'levels': [...]}; level l describes its
+    units, the distinct prefixes of length l that a sentence extends (by a label or by EOS):
+    `parent` (unit of level l-1; empty at level 0), `label` (the last label), and the outgoing edges
+    in CSR form, `edge_ptr` / `edge_label` / `edge_dst` with edge_dst >= 0 the unit of level l+1
+    the edge creates and -1 - s for the EOS edge of distinct sentence s.  Built by one row sort of
+    the padded sentence matrix and one pass of array operations per level."""
+    n_given = len(sentences)
+    lens = np.fromiter((len(s) for s in sentences), np.int64, n_given)
+    if n_given == 0:
+        return {'inverse': np.zeros(0, np.int64), 'count': 0, 'lengths': lens, 'levels': []}
+    width = int(lens.max()) + 1
+    mat = np.full((n_given, width), -1, np.int64)
+    flat = np.fromiter((c for s in sentences for c in s), np.int64, int(lens.sum()))
+    cols = np.arange(width)[None, :]
+    mat[cols < lens[:, None]] = flat
+    mat[np.arange(n_given), lens] = eos
+    mat, inverse = np.unique(mat, axis=0, return_inverse=True)       # rows in lexicographic order
+    inverse = np.asarray(inverse).reshape(-1)
+    m = mat.shape[0]
+    n = (mat >= 0).sum(1) - 1                                        # lengths without EOS
+    # differs[i, l]: row i and row i-1 differ somewhere in their first l columns
+    differs = np.ones((m, width + 1), bool)
+    differs[1:, 0] = False
+    differs[1:, 1:] = np.logical_or.accumulate(mat[1:] != mat[:-1], axis=1)
+    levels, unit_prev, prev = [], None, None
+    for l in range(int(n.max()) + 1):
+        active = np.nonzero(n >= l)[0]              # rows sharing a prefix of length l are adjacent
+        first = differs[active, l]
+        unit = np.full(m, -1, np.int64)
+        unit[active] = np.cumsum(first) - 1
+        heads = active[first]
+        level = {'n_units': int(first.sum()),
+                 'parent': unit_prev[heads] if l else np.zeros(0, np.int64),
+                 'label': mat[heads, l - 1] if l else np.zeros(0, np.int64)}
+        ends = active[n[active] == l]               # the sentences that end here: their EOS edges
+        level['_eos'] = (unit[ends], ends)
+        if prev is not None:
+            _close_level(prev, level, eos)
+        levels.append(level)
+        unit_prev, prev = unit, level
+    _close_level(prev, None, eos)
+    return {'inverse': inverse, 'count': m, 'lengths': n, 'levels': levels}
+
+
+def _close_level(level, nxt, eos):
+    """the CSR edge lists of `level` once the units of the next level are known"""
+    src_eos, sent = level.pop('_eos')
+    src = [src_eos, nxt['parent']] if nxt is not None else [src_eos]
+    lab = [np.full(len(sent), eos, np.int64)] + ([nxt['label']] if nxt is not None else [])
+    dst = [-1 - sent] + ([np.arange(nxt['n_units'])] if nxt is not None else [])
+    src, lab, dst = np.concatenate(src), np.concatenate(lab), np.concatenate(dst)
+    order = np.argsort(src, kind='stable')
+    level['edge_ptr'] = np.concatenate(([0], np.cumsum(np.bincount(src, minlength=level['n_units']))))
+    level['edge_label'], level['edge_dst'] = lab[order], dst[order]
+
+
+def batch_trie_levels(tries):
+    """The per-utterance tries of one call side by side: level l is as wide as the widest utterance
+    at that level, slot = utterance * width + unit; surplus slots are dead (they continue slot 0 of
+    their utterance and have no edges).  Sentence ids become global (offset by the distinct
+    sentences of the utterances before).  Returns (levels, sentence offsets); every level holds
+    `width`, `parent` / `label` [B * width] (parent indexes the previous level's slots; at level 0
+    the utterance), `edge_ptr` [B * width + 1], `edge_label` / `edge_dst` [edges] (global slots of
+    the next level, or -1 - global sentence) and `edge_src` [edges], the slot of every edge."""
+    B = len(tries)
+    offsets = np.concatenate(([0], np.cumsum([t['count'] for t in tries]))).astype(np.int64)
+    depth = max([len(t['levels']) for t in tries] + [0])
+    widths = [max([t['levels'][l]['n_units'] for t in tries if l < len(t['levels'])] + [1])
+              for l in range(depth)]
+    out = []
+    for l in range(depth):
+        W, Wp, Wn = widths[l], (widths[l - 1] if l else 1), (widths[l + 1] if l + 1 < depth else 1)
+        parent = np.repeat(np.arange(B) * Wp, W)                      # dead: slot 0 of the utterance
+        label = np.zeros(B * W, np.int64)
+        counts = np.zeros(B * W, np.int64)
+        e_lab, e_dst = [], []
+        for u, t in enumerate(tries):
+            if l >= len(t['levels']):
+                continue
+            lv = t['levels'][l]
+            k = lv['n_units']
+            if l:
+                parent[u * W:u * W + k] = u * Wp + lv['parent']
+                label[u * W:u * W + k] = lv['label']
+            counts[u * W:u * W + k] = np.diff(lv['edge_ptr'])
+            d = lv['edge_dst']
+            e_lab.append(lv['edge_label'])
+            e_dst.append(np.where(d >= 0, d + u * Wn, d - offsets[u]))
+        e_lab = np.concatenate(e_lab) if e_lab else np.zeros(0, np.int64)
+        e_dst = np.concatenate(e_dst) if e_dst else np.zeros(0, np.int64)
+        out.append({'width': W, 'parent': parent, 'label': label,
+                    'edge_ptr': np.concatenate(([0], np.cumsum(counts))),
+                    'edge_label': e_lab, 'edge_dst': e_dst,
+                    'edge_src': np.repeat(np.arange(B * W), counts)})
+    return out, offsets
+
+
+class DeviceForcedScorer(object):
+    """The bookkeeping of `AttentionDecoderTCN.score_sentences` on the MI355X: per trie level one
+    `asr_forced_level_f32` launch (coverage rows, log-partition, the fp64 acoustic carries, the
+    finished sentences' sums and covered-frame counts) and, with an LM, one
+    `asr_lm_bag_advance_f64` over the level's edges (one bag per edge row; a unit's bag is the row
+    of the edge that created it) followed by -logsumexp(-cost) of the EOS rows in fp64.  Every index
+    array of every level is uploaded once, before the first launch; `finish` reads everything back
+    in one copy.  Buffers are as wide as the widest level."""
+
+    def __init__(self, levels, n_sent, batch_size, device, num_classes, max_frames, enc_lens,
+                 coverage_tau, lm=None, alphabet_mapping=None):
+        from att_speech import _native
+        self._native = _native
+        self.levels, self.n_sent, self.batch_size = levels, int(n_sent), batch_size
+        self.num_classes, self.coverage_tau = num_classes, float(coverage_tau)
+        self._lens = torch.as_tensor(enc_lens).to(device, torch.int32).contiguous()
+        slots = max(batch_size * lv['width'] for lv in levels)
+        rows = max(max(len(lv['edge_label']) for lv in levels), 1)
+        self.rows = rows
+        self._use_lm = lm is not None
+        # ---- one upload of every level's indices (int32 for the launches, int64 for torch) ----
+        parts, self._where = [], []
+        at = 0
+        for l, lv in enumerate(levels):
+            arrays = {k: lv[k] for k in ('parent', 'label', 'edge_ptr', 'edge_label', 'edge_dst')}
+            eos = np.nonzero(lv['edge_dst'] < 0)[0]
+            arrays['eos_rows'], arrays['eos_sent'] = eos, -1 - lv['edge_dst'][eos]
+            if self._use_lm:
+                # the bag of a slot: row 0 (the start bag) at level 0, else the row of its edge
+                bag_row = np.zeros(batch_size * lv['width'], np.int64)
+                if l:
+                    made = np.nonzero(levels[l - 1]['edge_dst'] >= 0)[0]
+                    bag_row[levels[l - 1]['edge_dst'][made]] = made
+                adv_parent = np.zeros(rows, np.int64)
+                adv_input = np.full(rows, -1, np.int64)            # surplus rows: left alone
+                adv_parent[:len(lv['edge_src'])] = bag_row[lv['edge_src']]
+                adv_input[:len(lv['edge_label'])] = lv['edge_label']
+                arrays['adv_parent'], arrays['adv_input'] = adv_parent, adv_input
+            where = {}
+            for k, a in arrays.items():
+                where[k] = (at, at + len(a))
+                parts.append(np.asarray(a, np.int64))
+                at += len(a)
+            self._where.append(where)
+        host = np.concatenate(parts)
+        self._i64 = torch.from_numpy(host).to(device)
+        self._i32 = self._i64.to(torch.int32)
+        f64 = dict(dtype=torch.float64, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self._cov = [torch.zeros(slots, max_frames, device=device) for _ in range(2)]
+        self._ac = [torch.zeros(slots, **f64) for _ in range(2)]
+        self._sent = torch.zeros(3, max(self.n_sent, 1), **f64)       # acoustic, lm cost, covered
+        self._sent_cov = torch.zeros(max(self.n_sent, 1), **i32)
+        self._overflow = torch.zeros(1, **i32)
+        if self._use_lm:
+            bc = _native.LM_BAG_CAP
+            self._lmdev = lm.device_arrays(device)
+            self._mapping = torch.as_tensor(list(alphabet_mapping)).to(device, torch.int32).contiguous()
+            self._bags = [(torch.zeros(rows, bc, **i32), torch.zeros(rows, bc, **f64),
+                           torch.zeros(rows, **i32)) for _ in range(2)]
+            self._bags[0][0][0, 0] = lm.start()                       # row 0 = {start: 0}
+            self._bags[0][2][0] = 1
+            self._nsteps = torch.zeros(1, **i32)
+            self._slot = torch.arange(bc, device=device)[None, :]
+        self._level = 0
+
+    def index(self, l, key, long=False):
+        lo, hi = self._where[l][key]
+        return (self._i64 if long else self._i32)[lo:hi]
+
+    def step(self, logits, att, att_init=None):
+        """logits [B * width, C], att [B * width, T] of this level (att_init [B, T]: the initial
+        alignments, level 0 only).  Enqueues the launches of the level; nothing is read back."""
+        l, n = self._level, self._native
+        lv = self.levels[l]
+        i, o = l & 1, (l + 1) & 1
+        cov_in = att_init if l == 0 else self._cov[i]
+        n.forced_level(logits.reshape(-1, self.num_classes).contiguous(), att.contiguous(), cov_in,
+                       self._cov[o], self.index(l, 'parent'), self.index(l, 'edge_ptr'),
+                       self.index(l, 'edge_label'), self.index(l, 'edge_dst'), self._ac[i],
+                       self._ac[o], self._lens, self.batch_size, lv['width'], self.coverage_tau,
+                       self._sent[0], self._sent_cov)
+        if self._use_lm:
+            self._nsteps.add_(1)
+            n.lm_bag_advance(self._lmdev, self._mapping, self._bags[i], self._bags[o],
+                             self.index(l, 'adv_parent'), self.index(l, 'adv_input'), self._nsteps,
+                             l, 1, self.rows, self._overflow)
+            rows = self.index(l, 'eos_rows', long=True)
+            if rows.numel():
+                cost = self._bags[o][1].index_select(0, rows)
+                live = self._slot < self._bags[o][2].index_select(0, rows)[:, None]
+                neg = torch.where(live, -cost, torch.full_like(cost, float('-inf')))
+                self._sent[1].index_copy_(0, self.index(l, 'eos_sent', long=True),
+                                          -torch.logsumexp(neg, 1))
+        self._level = l + 1
+
+    def finish(self):
+        """-> (acoustic [n_sent] fp64, covered [n_sent] int64, lm cost [n_sent] fp64 or None,
+        overflow): the one read-back of the call."""
+        self._sent[2].copy_(self._sent_cov)
+        host = torch.cat((self._sent.reshape(-1), self._overflow.double())).cpu().numpy()
+        self.overflow = int(host[-1])
+        vals = host[:-1].reshape(3, -1)[:, :self.n_sent]
+        return (vals[0], vals[2].astype(np.int64), vals[1] if self._use_lm else None,
+                self.overflow)

@@ -4,7 +4,9 @@ the label history (`TCN` of `TemporalBlock`s, :46-116), a location-aware
 `LocalAttention` (:119-230) and `AttentionDecoderTCN` (:233-585) with the
 teacher-forced training `forward` (:357-440) and the step-wise beam `decode`
 (:442-585; plain BeamSearch, or with `lm_file` the LM-fused BeamSearchLM /
-RescoreSearchLM / GraphSearch over an att_speech.lm_fst.LmFst).
+RescoreSearchLM / GraphSearch over an att_speech.lm_fst.LmFst), plus
+`score_sentences`, the teacher-forced rescoring pass of the reference's
+egs/wsj/local/lattice_search scripts.
 
 Kept from the reference: class names, constructor keywords, the returned dicts
 and the checkpoint keys (`tcn.network.<i>.net.conv<j>.{bias,weight_g,weight_v}`,
@@ -25,10 +27,12 @@ from __future__ import absolute_import, division, print_function
 import os
 import warnings
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
+from att_speech import fst_utils
 from att_speech.lm_fst import LmFst
 from att_speech.modules.beam_search import (BeamSearch, BeamSearchLM, GraphSearch,
                                              RescoreSearchLM)
@@ -666,4 +670,182 @@ class AttentionDecoderTCN(nn.Module):
         if return_attention:
             out.update(attweights=trace_att, logits=trace_logits)
         out.update(coverage=search.coverage, graph=search.get_graph(), beam_search=search)
+        return out
+
+    # ---------------------------------------------------------------- forced scoring
+    def _check_sentences(self, sentences, batch_size):
+        if len(sentences) != batch_size:
+            raise ValueError('score_sentences: %d sentence lists for %d utterances'
+                             % (len(sentences), batch_size))
+        for per_utt in sentences:
+            for sent in per_utt:
+                if len(sent) == 0:
+                    raise ValueError('score_sentences: an empty sentence')
+                for c in sent:
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+                        raise ValueError('score_sentences: labels must be integers, got %r' % (c,))
+                    if not 0 <= c < self.EOS:
+                        raise ValueError('score_sentences: label %d outside [0, %d) (EOS is appended '
+                                         'here)' % (c, self.EOS))
+
+    def _native_forced_ok(self, encoded):
+        """The device path of score_sentences (DeviceForcedScorer) takes what the decode step takes:
+        a cuda fp32 encoder output of at most _STEP_MAX_FRAMES frames, 32 filter taps, no window or
+        one the step accepts (_native_window_ok), and an LM, if any, whose epsilon graph is acyclic
+        and whose labels fit the classes.  ASR_FORCED_NATIVE=0, read per call, keeps the host loop;
+        the device path is the default at every size, a single sentence included (it measured
+        1.6x the host loop there)."""
+        if os.environ.get('ASR_FORCED_NATIVE', '1') == '0':
+            return False
+        if not (encoded.is_cuda and encoded.dtype == torch.float32 and self.attn.kernel_size == 32
+                and 1 <= encoded.size(0) <= _STEP_MAX_FRAMES and 2 <= self.num_classes <= 2048
+                and self._native_window_ok()):
+            return False
+        if self.lm is not None:
+            lm = self.lm
+            if (lm.eps_rank() is None or not len(lm.ilabel)
+                    or int(lm.ilabel.max()) >= self.num_classes
+                    or lm.device_arrays(encoded.device) is None):
+                return False
+        return True
+
+    def _score_lm_host(self, sent):
+        """score_lm of the scripts: the cost of the bag after the sentence and EOS"""
+        bag = {self.lm.start(): 0}
+        for c in list(sent) + [self.EOS]:
+            bag = fst_utils.expand(self.lm, bag, self.alphabet_mapping[c], use_log_probs=True)
+        return fst_utils.reduce_weights(bag.values(), True)
+
+    def _score_sentences_host(self, encoded, lens, sentences):
+        """The per-sentence loop of the scripts (score_acoustic / score_lm): every sentence on its
+        own, batch 1, on the utterance's own frames; one read-back per sentence.
+        -> per utterance (acoustic, covered frames, LM cost or None)."""
+        out = []
+        beam, self.beam_size = self.beam_size, 1        # enc_initial_state repeats lens by it
+        try:
+            for u, per_utt in enumerate(sentences):
+                enc_u = encoded[:lens[u], u:u + 1].contiguous()
+                acoustic, covered = np.zeros(len(per_utt)), np.zeros(len(per_utt), np.int64)
+                lm = np.zeros(len(per_utt)) if self.lm is not None else None
+                for j, sent in enumerate(per_utt):
+                    state = self.enc_initial_state(enc_u, torch.tensor([lens[u]]), 1, 1)
+                    cov = state['att_weights'].clone()
+                    terms = []
+                    for c in list(sent) + [self.EOS]:
+                        history = state['inputs']
+                        logits, state = self.enc_step(**state)
+                        cov = cov + state['att_weights']
+                        terms.append(F.log_softmax(logits[0, 0], dim=-1)[c])
+                        new_input = torch.tensor([c], device=encoded.device)
+                        state['inputs'] = torch.cat((history[1:], self.embedding(new_input)[None]))
+                    k = (cov[:, 0] > self.coverage_tau).sum()
+                    host = torch.cat((torch.stack(terms).double(), k.double()[None])).cpu().tolist()
+                    acoustic[j] = sum(host[:-1])                  # fp64, in position order
+                    covered[j] = int(host[-1])
+                    if lm is not None:
+                        lm[j] = self._score_lm_host(sent)
+                out.append((acoustic, covered, lm))
+        finally:
+            self.beam_size = beam
+        return out
+
+    def _score_sentences_native(self, encoded, lens, sentences):
+        """The device path: the sentences of every utterance as a prefix trie, one label step per
+        trie LEVEL for all distinct prefixes of that length (the body of _decode_native with the
+        forced bookkeeping of DeviceForcedScorer in place of a search), nothing read back before the
+        end.  None when an LM bag outgrew the device's cap."""
+        from att_speech import _native
+        from att_speech.modules import beam_search as bs
+        T, B, E = encoded.shape
+        dev, attn = encoded.device, self.attn
+        tries = [bs.sentence_trie(per_utt, self.EOS) for per_utt in sentences]
+        levels, offsets = bs.batch_trie_levels(tries)
+        lens_dev = torch.as_tensor(lens).to(dev, torch.int32)
+        scorer = bs.DeviceForcedScorer(levels, offsets[-1], B, dev, self.num_classes, T, lens_dev,
+                                       self.coverage_tau, lm=self.lm,
+                                       alphabet_mapping=self.alphabet_mapping)
+        (eproj, _), first = attn.init_attention(encoded, lens_dev)
+        eproj, enc = eproj.contiguous(), encoded.contiguous()
+        att0 = first.t().contiguous()                                          # [B, T]
+        plan = self.tcn.last_step_plan(self.tcn.eff_history)
+        w_att = torch.cat((attn.lm_to_kernel.weight, attn.lm_to_global.weight)).detach()
+        b_att = torch.cat((attn.lm_to_kernel.bias, attn.lm_to_global.bias)).detach()
+        n_filt = attn.lm_to_kernel.out_features
+        w_score = attn.hidden_to_score.weight.detach().reshape(-1).contiguous()
+        b_score = float(attn.hidden_to_score.bias)
+        window = tuple(attn.force_forward) if attn.force_forward else None
+        history = enc.new_zeros(self.tcn.eff_history, B, self.tcn_hidden_size)
+        att = att0
+        for l, lv in enumerate(levels):
+            if l:
+                history = torch.cat((history[1:].index_select(1, scorer.index(l, 'parent', long=True)),
+                                     self.embedding(scorer.index(l, 'label', long=True))[None]))
+            lm_state = TCN.last_step(history, plan)
+            fg = torch.addmm(b_att, lm_state, w_att.t())
+            att, context = _native.tcn_attention_step(
+                eproj, enc, lens_dev, fg[:, :n_filt].contiguous(), fg[:, n_filt:].contiguous(),
+                w_score, b_score, attn.temperature, att, scorer.index(l, 'parent'), lv['width'],
+                window=window)
+            scorer.step(self._step_output(lm_state, context), att, att_init=att0)
+        acoustic, covered, lm, overflow = scorer.finish()
+        if overflow:
+            self._native_gave_up = ('lm_bag_overflow', overflow, _native.LM_BAG_CAP)
+            return None
+        out = []
+        for u, t in enumerate(tries):
+            pick = offsets[u] + t['inverse']
+            out.append((acoustic[pick], covered[pick], lm[pick] if lm is not None else None))
+        return out
+
+    def score_sentences(self, encoded, encoded_lens, sentences, coverage='log_fraction'):
+        """Teacher-forced scores of given sentences: `rescore2` of the reference's
+        egs/wsj/local/lattice_search/rescore_lattices2.py (coverage='log_fraction') and
+        score_groundtruth.py (coverage='count').  encoded [T', B, E]; `sentences` holds per utterance
+        a list of label-id lists (no EOS, none empty, labels in [0, num_classes - 1)).  Every
+        utterance is scored on its own encoded_lens[u] frames, as a batch-1 call would.  Returns per
+        utterance a dict of fp64 arrays with one value per sentence, in the given order:
+          acoustic  sum over the positions 0..n of log_softmax(logits_i)[y_i], y_n = EOS (fp32 terms,
+                    summed in fp64 in position order);
+          coverage  with k = the frames whose summed alignments (the initial one included) exceed
+                    coverage_tau (returned as `covered`): coverage_weight * log(k / len), or
+                    coverage_weight * k for 'count';
+          lm        -lm_weight * cost of the LM bag after the sentence and EOS (0.0 without an LM);
+          loss      (acoustic + coverage + lm) / n ** length_normalization.
+        On the MI355X the sentences are scored through their prefix trie (_score_sentences_native);
+        CPU models, ASR_FORCED_NATIVE=0 and the shapes the decode step refuses take the per-sentence
+        host loop, as does a call in which an LM bag outgrows the device's cap (one warning)."""
+        if coverage not in ('log_fraction', 'count'):
+            raise ValueError("score_sentences: coverage must be 'log_fraction' or 'count'")
+        if self.training:
+            raise RuntimeError('score_sentences needs eval() mode')
+        lens = [int(v) for v in torch.as_tensor(encoded_lens).tolist()]
+        sentences = [[[c for c in sent] for sent in per_utt] for per_utt in sentences]
+        self._check_sentences(sentences, encoded.size(1))
+        total = sum(len(per_utt) for per_utt in sentences)
+        with torch.no_grad():
+            parts = None
+            if total and self._native_forced_ok(encoded):
+                parts = self._score_sentences_native(encoded, lens, sentences)
+                if parts is None:
+                    from att_speech import _native
+                    why, asked, cap = self._native_gave_up
+                    if not _native._WARNED.get('forced_' + why):
+                        _native._WARNED['forced_' + why] = True
+                        warnings.warn('an LM bag of the device forced scorer asked for at least %d '
+                                      'states, above its cap of %d: scoring this call with the host '
+                                      'loop, one sentence at a time' % (asked, cap))
+            if parts is None:
+                parts = self._score_sentences_host(encoded, lens, sentences)
+        out = []
+        for u, (acoustic, covered, lm_cost) in enumerate(parts):
+            n = np.array([len(sent) for sent in sentences[u]], np.float64)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                if coverage == 'count':
+                    cov = self.coverage_weight * covered.astype(np.float64)
+                else:
+                    cov = self.coverage_weight * np.log(covered / float(lens[u]))
+                lm = -self.lm_weight * lm_cost if lm_cost is not None else np.zeros(len(n))
+                loss = (acoustic + cov + lm) / n ** self.length_normalization
+            out.append({'acoustic': acoustic, 'coverage': cov, 'lm': lm, 'loss': loss,
+                        'covered': covered})
         return out
