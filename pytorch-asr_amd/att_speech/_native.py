@@ -1215,39 +1215,30 @@ def lm_bag_advance(lm, mapping, bags_in, bags_out, parent, new_input, nsteps, st
 
 def beam_lm_step(logits, att, lens, lm_cost, lm_weight, scores_in, scores_out, est_in, est_out, cov_in,
                  cov_out, min_eos, step, B, beam, len_div, min_attention_pos, coverage_tau,
-                 coverage_weight, state):
+                 coverage_weight, state, fin_mask=None, tot_out=None):
     """asr_beam_lm_step_f32; `state` = dict of the per-utterance device arrays (fin_count, fin_parity,
     fin_score, fin_len, fin_beam, fin_tokens, best_score, best_len, best_tokens, best_elems,
-    new_input, parent, frozen, nsteps)."""
+    new_input, parent, frozen, nsteps).  With either of fin_mask [hyps] i32 / tot_out [hyps] f32
+    given, asr_beam_lm_step_graph_f32: the same step plus those two outputs."""
     C, T = logits.shape[-1], att.shape[-1]
-    check(lib().asr_beam_lm_step_f32(
+    graph = fin_mask is not None or tot_out is not None
+    name = 'asr_beam_lm_step_graph_f32' if graph else 'asr_beam_lm_step_f32'
+    extra = (_p(fin_mask), _p(tot_out)) if graph else ()
+    check(getattr(lib(), name)(
         _p(logits), _p(att), _p(lens), _p(lm_cost), float(lm_weight), _p(scores_in), _p(scores_out),
         _p(est_in), _p(est_out), _p(cov_in), _p(cov_out), _p(min_eos), step, B, beam, C, T,
         est_in.shape[1], len_div, float(min_attention_pos), coverage_tau, coverage_weight,
         _p(state['fin_count']), _p(state['fin_parity']), _p(state['fin_score']), _p(state['fin_len']),
         _p(state['fin_beam']), _p(state['fin_tokens']), _p(state['best_score']), _p(state['best_len']),
         _p(state['best_tokens']), _p(state['best_elems']), _p(state['new_input']), _p(state['parent']),
-        _p(state['frozen']), _p(state['nsteps']), _stream()), 'asr_beam_lm_step_f32')
+        _p(state['frozen']), _p(state['nsteps']), *(extra + (_stream(),))), name)
+
+
+beam_lm_step_graph = beam_lm_step       # positional callers: the same wrapper with both outputs given
 
 
 def graph_search_supported(beam, span, T, bag_cap=LM_BAG_CAP):
     return bool(lib().asr_graph_search_supported(beam, span, T, bag_cap))
-
-
-def beam_lm_step_graph(logits, att, lens, lm_cost, lm_weight, scores_in, scores_out, est_in, est_out, cov_in,
-                       cov_out, min_eos, step, B, beam, len_div, min_attention_pos, coverage_tau,
-                       coverage_weight, state, fin_mask, tot_out):
-    """asr_beam_lm_step_graph_f32: beam_lm_step plus fin_mask [hyps] i32 and tot_out [hyps] f32."""
-    C, T = logits.shape[-1], att.shape[-1]
-    check(lib().asr_beam_lm_step_graph_f32(
-        _p(logits), _p(att), _p(lens), _p(lm_cost), float(lm_weight), _p(scores_in), _p(scores_out),
-        _p(est_in), _p(est_out), _p(cov_in), _p(cov_out), _p(min_eos), step, B, beam, C, T,
-        est_in.shape[1], len_div, float(min_attention_pos), coverage_tau, coverage_weight,
-        _p(state['fin_count']), _p(state['fin_parity']), _p(state['fin_score']), _p(state['fin_len']),
-        _p(state['fin_beam']), _p(state['fin_tokens']), _p(state['best_score']), _p(state['best_len']),
-        _p(state['best_tokens']), _p(state['best_elems']), _p(state['new_input']), _p(state['parent']),
-        _p(state['frozen']), _p(state['nsteps']), _p(fin_mask), _p(tot_out), _stream()),
-        'asr_beam_lm_step_graph_f32')
 
 
 NODE_KEYS = ('node_count', 'node_score', 'node_len', 'node_tokens', 'node_att', 'node_bag_n',

@@ -80,26 +80,12 @@ class BeamSearch(object):
     def step(self, logits, *args, **kwargs):
         """(:147-175) logits [1, B*beam, C] -> (new input ids [B*beam],
         state mapping [B*beam])."""
-        B, beam, C = self.batch_size, self.beam_size, self.num_classes
         local_scores = torch.nn.functional.log_softmax(logits.squeeze(0), dim=1)
-        global_scores = local_scores + self.scores.unsqueeze(1).repeat(1, C)
+        global_scores = local_scores + self.scores.unsqueeze(1).repeat(1, self.num_classes)
         if self.estimations is not None:
             self._save_best_finished(global_scores)
-        # ignore EOS from now on (:126-133); first step: beam 0 only
-        gs = global_scores[:, :-1].contiguous().view(B, -1)
-        if self.estimations is None:
-            gs = gs[:, :C - 1]
-        new_scores, best_it = self._get_topk(gs)
-        # re-index the hypotheses (:108-124), vectorised
-        best_beams = best_it // (C - 1)
-        best_letters = best_it % (C - 1)
-        base = (torch.arange(B, device=best_it.device) * beam)[:, None]
-        mapping = (base + best_beams).view(-1)
-        if self.estimations is None:
-            est = torch.zeros((B * beam, 0), dtype=torch.long, device=best_it.device)
-        else:
-            est = self.estimations[mapping]
-        self.estimations = torch.cat((est, best_letters.reshape(-1, 1)), dim=1)
+        new_scores, best_it = self._get_topk(self._do_ignore_eos(global_scores))
+        mapping, self.estimations, best_letters = self._compute_new_beam(best_it)
         self.scores = new_scores.reshape(-1)
         return best_letters.reshape(-1), mapping
 
@@ -117,6 +103,7 @@ class BeamSearch(object):
         return ''.join(itos[e] if itos[e] != '<spc>' else ' ' for e in est)
 
     def _do_ignore_eos(self, global_scores):
+        """(:126-133) ignore EOS from now on; first step: beam 0 only"""
         global_scores = global_scores[:, :-1].contiguous().view(self.batch_size, -1)
         if self.estimations is None:
             global_scores = global_scores[:, :self.num_classes - 1]
@@ -470,6 +457,22 @@ def merge_graphs(graph):
     return G
 
 
+def best_result(search):
+    """the three keys every `decode` returns, from a search that has finished"""
+    return {'decoded': search.best_finished,
+            'decoded_scores': search.best_finished_scores_elements,
+            'loss': torch.Tensor(search.best_finished_scores).mean()}
+
+
+def _read_best_finished(search, st):
+    """`best_finished` / `best_finished_scores` of a device search from its state arrays `st`"""
+    lens = st['best_len'].cpu().tolist()
+    toks = st['best_tokens'].cpu().long()
+    search.best_finished = [toks[b, :lens[b]] if lens[b] > 0 else []
+                            for b in range(search.batch_size)]
+    search.best_finished_scores = [float(v) for v in st['best_score'].cpu().tolist()]
+
+
 class DeviceBeamSearch(object):
     """Plain BeamSearch (reference beam_search.py:13-182) with ALL of its state on the MI355X
     and no host read-back inside a step (`asr_beam_step_f32`): running scores, label
@@ -527,10 +530,7 @@ class DeviceBeamSearch(object):
         done = st['done'].cpu().tolist()
         eff = int(done[2])                       # steps that took effect
         self.finished_count = st['finished_count'].cpu().tolist()
-        lens = st['best_len'].cpu().tolist()
-        toks = st['best_tokens'].cpu().long()
-        self.best_finished = [toks[b, :lens[b]] if lens[b] > 0 else [] for b in range(self.batch_size)]
-        self.best_finished_scores = [float(v) for v in st['best_score'].cpu().tolist()]
+        _read_best_finished(self, st)
         self.best_finished_scores_elements = {'acoustic': self.best_finished_scores}
         self.estimations = self._est[eff & 1][:, :eff].long()
         self.scores = self._scores[eff & 1]
@@ -567,9 +567,8 @@ class DeviceBeamSearchLM(object):
         self.keep_eos_score = keep_eos_score
         B, beam, cap, T = batch_size, beam_size, max_steps + 1, max_frames
         hyps, bc = B * beam, _native.LM_BAG_CAP
-        i32 = dict(dtype=torch.int32, device=device)
-        z = lambda *s: torch.zeros(*s, device=device)  # noqa: E731
-        zi = lambda *s: torch.zeros(*s, **i32)  # noqa: E731
+        z = self._z = lambda *s: torch.zeros(*s, device=device)  # noqa: E731
+        zi = self._zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)  # noqa: E731
         self._lens = torch.as_tensor(enc_lens).to(device, torch.int32).contiguous()
         self._scores = [z(hyps), z(hyps)]
         self._est = [zi(hyps, cap), zi(hyps, cap)]
@@ -598,6 +597,7 @@ class DeviceBeamSearchLM(object):
         self._state['frozen'] = self._state['flags'][:B]
         self._state['overflow'] = self._state['flags'][B:]
         self._step = 0
+        self._step_outputs = ()         # a subclass's (fin_mask, tot_out): the graph step entry
         self.overflow = 0
         self.print_debug = False
         self.estimations = None
@@ -618,12 +618,16 @@ class DeviceBeamSearchLM(object):
         n.beam_lm_step(logits, att, self._lens, self._cost, self.lm_weight, self._scores[i],
                        self._scores[o], self._est[i], self._est[o], self._cov[i], self._cov[o],
                        self._min_eos, s, B, beam, len_div, self.min_attention_pos, self.coverage_tau,
-                       self.coverage_weight, st)
+                       self.coverage_weight, st, *self._step_outputs)
         if self._use_lm:
             n.lm_bag_advance(self._lmdev, self._mapping, self._bags[i], self._bags[o], st['parent'],
                              st['new_input'], st['nsteps'], s, B, beam, st['overflow'])
+        self._after_advance(att, s)
         self._step = s + 1
         return st['new_input'], st['parent']
+
+    def _after_advance(self, att, s):
+        """what a subclass enqueues behind the step of label position `s`, once the bags advanced"""
 
     def poll_finished(self):
         """True when every utterance is frozen or a bag overflowed (`self.overflow` = its size)."""
@@ -641,10 +645,7 @@ class DeviceBeamSearchLM(object):
         B, beam = self.batch_size, self.beam_size
         self.overflow = int(st['overflow'][0])
         eff = st['nsteps'].tolist()                  # steps that took effect, per utterance
-        lens = st['best_len'].tolist()
-        toks = st['best_tokens'].long()
-        self.best_finished = [toks[b, :lens[b]] if lens[b] > 0 else [] for b in range(B)]
-        self.best_finished_scores = [float(v) for v in st['best_score'].tolist()]
+        _read_best_finished(self, st)
         el = st['best_elems'].tolist()
         self.best_finished_scores_elements = {'acoustic': [el[b][0] for b in range(B)],
                                               'lm': [el[b][1] for b in range(B)]}
@@ -686,6 +687,15 @@ class DeviceBeamSearchLM(object):
 GRAPH_STORE_BUDGET_BYTES = 2 << 30
 
 
+class GraphStoreOverBudget(MemoryError):
+    """what DeviceGraphSearch raises in place of allocating such a store; carries both figures"""
+
+    def __init__(self, need, budget):
+        super(GraphStoreOverBudget, self).__init__(
+            'a node store of %d bytes is above the budget of %d' % (need, budget))
+        self.need, self.budget = need, budget
+
+
 class DeviceGraphSearch(DeviceBeamSearchLM):
     """GraphSearch (reference beam_search.py:406-648) on the MI355X for any number of utterances: B
     utterances behave as B independent GraphSearch(batch_size=1) runs.  Per label step
@@ -704,9 +714,8 @@ class DeviceGraphSearch(DeviceBeamSearchLM):
                  num_classes, length_normalization, max_steps, max_frames, enc_lens,
                  keep_eos_score=False):
         need = self.store_bytes(batch_size, beam_size, max_steps, max_frames)
-        if need > GRAPH_STORE_BUDGET_BYTES:
-            raise MemoryError('a node store of %d bytes is above the budget of %d'
-                              % (need, GRAPH_STORE_BUDGET_BYTES))
+        if need > GRAPH_STORE_BUDGET_BYTES:              # the one check, before anything is allocated
+            raise GraphStoreOverBudget(need, GRAPH_STORE_BUDGET_BYTES)
         super(DeviceGraphSearch, self).__init__(
             lm, lm_weight, alphabet_mapping, min_attention_pos, coverage_tau, coverage_weight,
             batch_size, beam_size, device, num_classes, length_normalization, max_steps, max_frames,
@@ -714,15 +723,15 @@ class DeviceGraphSearch(DeviceBeamSearchLM):
         self.hash_dec, self.merge_threshold, self.span = hash_dec, float(merge_threshold), int(span)
         B, beam, cap, T = batch_size, beam_size, max_steps + 1, max_frames
         ncap, bc = max_steps * beam, self._native.LM_BAG_CAP
-        zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)  # noqa: E731
-        self._fin_mask = zi(B * beam)
-        self._tot = torch.zeros(B * beam, device=device)
+        z, zi = self._z, self._zi
+        self._fin_mask, self._tot = zi(B * beam), z(B * beam)
+        self._step_outputs = (self._fin_mask, self._tot)
         self._len_pow = torch.tensor([float(l ** length_normalization) for l in range(cap + 1)],
                                      dtype=torch.float32, device=device)
         self._store = {
-            'node_count': zi(B), 'node_score': torch.zeros(B, ncap, device=device),
+            'node_count': zi(B), 'node_score': z(B, ncap),
             'node_len': zi(B, ncap), 'node_tokens': zi(B, ncap, cap),
-            'node_att': torch.zeros(B, ncap, T, device=device), 'node_bag_n': zi(B, ncap),
+            'node_att': z(B, ncap, T), 'node_bag_n': zi(B, ncap),
             'node_bag_state': zi(B, ncap, bc), 'node_fin': zi(B, ncap),
             'node_uplink': torch.full((B, ncap), -1, dtype=torch.int32, device=device)}
         self.graph = [{} for _ in range(B)]
@@ -734,29 +743,17 @@ class DeviceGraphSearch(DeviceBeamSearchLM):
         return batch_size * (4 + max_steps * beam_size * per_node)
 
     def step(self, logits, att_weights, *args, **kwargs):
-        s, n, st = self._step, self._native, self._state
-        B, beam = self.batch_size, self.beam_size
-        assert (s + 1) * beam <= self._store['node_score'].shape[1]     # the store cannot overflow
-        logits = logits.reshape(-1, self.num_classes).contiguous()
-        att = att_weights.contiguous()
-        len_div = float(s ** self.length_normalization) if s > 0 else 1.0
-        i, o = s & 1, (s + 1) & 1
-        if self._use_lm:
-            n.lm_label_costs(self._lmdev, *self._bags[i], self._mapping, st['frozen'], B, beam,
-                             self.num_classes, self._cost)
-        n.beam_lm_step_graph(logits, att, self._lens, self._cost, self.lm_weight, self._scores[i],
-                             self._scores[o], self._est[i], self._est[o], self._cov[i], self._cov[o],
-                             self._min_eos, s, B, beam, len_div, self.min_attention_pos,
-                             self.coverage_tau, self.coverage_weight, st, self._fin_mask, self._tot)
-        if self._use_lm:
-            n.lm_bag_advance(self._lmdev, self._mapping, self._bags[i], self._bags[o], st['parent'],
-                             st['new_input'], st['nsteps'], s, B, beam, st['overflow'])
+        """DeviceBeamSearchLM's step through the graph entry (`_step_outputs`), then the merge."""
+        assert (self._step + 1) * self.beam_size <= self._store['node_score'].shape[1]   # the store cannot overflow
+        return super(DeviceGraphSearch, self).step(logits, att_weights)
+
+    def _after_advance(self, att, s):
+        B, beam, i, o = self.batch_size, self.beam_size, s & 1, (s + 1) & 1
         if beam > 1:
-            n.graph_merge(att, self._lens, self._scores[o], self._tot, self._est[i], self._est[o],
-                          self._fin_mask, self._bags[o] if self._use_lm else None, st['nsteps'],
-                          self._len_pow, s, B, beam, self.span, self.merge_threshold, self._store)
-        self._step = s + 1
-        return st['new_input'], st['parent']
+            self._native.graph_merge(
+                att, self._lens, self._scores[o], self._tot, self._est[i], self._est[o],
+                self._fin_mask, self._bags[o] if self._use_lm else None, self._state['nsteps'],
+                self._len_pow, s, B, beam, self.span, self.merge_threshold, self._store)
 
     def finalize(self):
         super(DeviceGraphSearch, self).finalize()

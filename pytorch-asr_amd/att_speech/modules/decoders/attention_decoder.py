@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from att_speech.lm_fst import LmFst
-from att_speech.modules.beam_search import BeamSearch, BeamSearchLM, GraphSearch
+from att_speech.modules.beam_search import BeamSearch, BeamSearchLM, GraphSearch, best_result
 from att_speech.utils import get_mask
 
 _MASKED = 1e5       # what a padding frame's score is lowered by
@@ -299,9 +299,7 @@ class AttentionDecoderRNN(nn.Module):
                 if step % poll_every == poll_every - 1 and search.poll_finished():
                     break
         search.finalize()
-        return {'decoded': search.best_finished,
-                'decoded_scores': search.best_finished_scores_elements,
-                'loss': torch.Tensor(search.best_finished_scores).mean()}
+        return best_result(search)
 
     def decode(self, encoded, encoded_lens, texts=None, text_lens=None, print_debug=False,
                **kwargs):
@@ -326,9 +324,7 @@ class AttentionDecoderRNN(nn.Module):
             alignment = alignment[:, parent]
             if search.has_finished():
                 break
-        return {'decoded': search.best_finished,
-                'decoded_scores': search.best_finished_scores_elements,
-                'loss': torch.Tensor(search.best_finished_scores).mean()}
+        return best_result(search)
 
     def single_step(self, word_input, last_hidden, encoder_outputs, encoded_lens,
                     precomputed_V_enc_out):

@@ -34,6 +34,7 @@ from torch import nn
 
 from att_speech import fst_utils
 from att_speech.lm_fst import LmFst
+from att_speech.modules import beam_search as bs
 from att_speech.modules.beam_search import (BeamSearch, BeamSearchLM, GraphSearch,
                                              RescoreSearchLM)
 
@@ -263,6 +264,64 @@ class _AttentionScan(torch.autograd.Function):
 
 _SMOOTHING_TAPS = (0.005, 0.02, 0.95, 0.02, 0.005)      # along the label axis (:411-414)
 
+# one warning per process and key (`_native._WARNED`) when a device path gives a call up
+_GAVE_UP_WARNINGS = {
+    'graph_store': 'the node store of the device graph search would take %d bytes, above its '
+                   'budget of %d: decoding this call with the host GraphSearch, one utterance '
+                   'at a time',
+    'lm_bag_overflow': 'an LM bag of the device beam search asked for at least %d states, above '
+                       'its cap of %d: decoding this call with the host BeamSearchLM, one utterance at a time',
+    'forced_lm_bag_overflow': 'an LM bag of the device forced scorer asked for at least %d '
+                              'states, above its cap of %d: scoring this call with the host '
+                              'loop, one sentence at a time'}
+
+
+class _DeviceStepper(object):
+    """The label step of AttentionDecoderTCN on the MI355X, the one place both device paths
+    (`_decode_native`, `_score_sentences_native`) take it from.  Built once per call: the
+    per-utterance operands (the reference repeats them per hypothesis, :449-456), the
+    last-frame plan of the TCN and the filter / global weights as one matrix.  `step` is the LM
+    state of the last frame as dense products (TCN.last_step), ONE launch for the local
+    attention + context (asr_tcn_attention_step_f32, or asr_tcn_attention_step_win_f32 under a
+    force_forward window) and the output MLP; `roll` moves the label history on.  Nothing
+    here reads back from the device after the constructor."""
+
+    def __init__(self, decoder, encoded, lens_dev):
+        attn, tcn = decoder.attn, decoder.tcn
+        self.decoder, self.lens = decoder, lens_dev
+        (eproj, _), self.first = attn.init_attention(encoded, lens_dev)   # first: [T, B]
+        self.eproj, self.enc = eproj.contiguous(), encoded.contiguous()
+        self.plan = tcn.last_step_plan(tcn.eff_history)
+        self.w_att = torch.cat((attn.lm_to_kernel.weight, attn.lm_to_global.weight)).detach()
+        self.b_att = torch.cat((attn.lm_to_kernel.bias, attn.lm_to_global.bias)).detach()
+        self.n_filt = attn.lm_to_kernel.out_features
+        self.w_score = attn.hidden_to_score.weight.detach().reshape(-1).contiguous()
+        self.b_score = float(attn.hidden_to_score.bias)
+        self.window = tuple(attn.force_forward) if attn.force_forward else None
+
+    def empty_history(self, rows):
+        tcn = self.decoder.tcn
+        return self.enc.new_zeros(tcn.eff_history, rows, self.decoder.tcn_hidden_size)
+
+    def step(self, history, att_prev, parent, group):
+        """history [eff_history, rows, D]; att_prev [rows', T] with row r of the output continuing
+        row parent[r] of it (None: its own row); `group` rows per utterance -> (logits [rows, C],
+        alignment [rows, T])."""
+        from att_speech import _native
+        n_filt = self.n_filt
+        lm_state = TCN.last_step(history, self.plan)
+        fg = torch.addmm(self.b_att, lm_state, self.w_att.t())
+        att, context = _native.tcn_attention_step(
+            self.eproj, self.enc, self.lens, fg[:, :n_filt].contiguous(), fg[:, n_filt:].contiguous(),
+            self.w_score, self.b_score, self.decoder.attn.temperature, att_prev, parent, group,
+            window=self.window)
+        return self.decoder._step_output(lm_state, context), att
+
+    def roll(self, history, parent, labels):
+        """the history of the rows that continue rows `parent` with `labels`"""
+        return torch.cat((history[1:].index_select(1, parent.long()),
+                          self.decoder.embedding(labels.long())[None]))
+
 
 class AttentionDecoderTCN(nn.Module):
     def __init__(self, sample_batch, num_classes, tcn_hidden_size, att_hidden_size,
@@ -323,9 +382,7 @@ class AttentionDecoderTCN(nn.Module):
 
     def hash_dec(self, decoded):
         """Merge key of GraphSearch (:335-345): the last `history` labels, left-filled with -1."""
-        span = self.graph_search_history_len
-        if span < 0:
-            span = self.tcn.eff_history
+        span = self._graph_span()
         if span == 0:
             return 0
         tail = decoded[-span:].tolist()
@@ -452,6 +509,27 @@ class AttentionDecoderTCN(nn.Module):
                                keep_eos_score=self.keep_eos_score)
         return BeamSearchLM(*fused, keep_eos_score=self.keep_eos_score)
 
+    def _make_device_search(self, B, dev, lens, T):
+        """The device search of this model for B utterances of at most T frames (`lens` on the
+        device): DeviceBeamSearch, with an LM DeviceBeamSearchLM, with use_graph_search
+        DeviceGraphSearch — or None, with `_native_gave_up` saying so, when the graph search
+        refuses its node store (before anything is allocated)."""
+        plain = (B, self.beam_size, dev, self.num_classes, self.length_normalization,
+                 self.TRANSCRIPTION_LEN_GUARD)
+        if not self.lm:
+            return bs.DeviceBeamSearch(*plain)
+        fused = (self.lm, self.lm_weight, self.alphabet_mapping, self.min_attention_pos,
+                 self.coverage_tau, self.coverage_weight) + plain + (T, lens)
+        if not self.use_graph_search:
+            return bs.DeviceBeamSearchLM(*fused, keep_eos_score=self.keep_eos_score)
+        try:
+            return bs.DeviceGraphSearch(self.hash_dec, self.graph_search_merge_threshold,
+                                        self._graph_span(), *fused,
+                                        keep_eos_score=self.keep_eos_score)
+        except bs.GraphStoreOverBudget as refused:
+            self._native_gave_up = ('graph_store', refused.need, refused.budget)
+            return None
+
     def _native_window_ok(self):
         """The device decode step takes no window, or a force_forward (lo, hi) of integers with
         lo < hi and hi >= 1 (asr_tcn_attention_step_win_f32; with hi < 1 the reference's
@@ -498,10 +576,14 @@ class AttentionDecoderTCN(nn.Module):
             return False
         if self.lm_weight == 0 and not self.coverage_weight > 0:
             return False
+        return bool(encoded.is_cuda and self._lm_fits_device(encoded))
+
+    def _lm_fits_device(self, encoded):
+        """the LM's epsilon graph is acyclic, its labels fit the classes, its arrays the device"""
         lm = self.lm
-        if lm.eps_rank() is None or not len(lm.ilabel) or int(lm.ilabel.max()) >= self.num_classes:
-            return False
-        return bool(encoded.is_cuda and lm.device_arrays(encoded.device) is not None)
+        return not (lm.eps_rank() is None or not len(lm.ilabel)
+                    or int(lm.ilabel.max()) >= self.num_classes
+                    or lm.device_arrays(encoded.device) is None)
 
     def _graph_span(self):
         """the number of labels in GraphSearch's merge key (hash_dec)"""
@@ -520,70 +602,32 @@ class AttentionDecoderTCN(nn.Module):
         (DeviceBeamSearchLM: asr_lm_label_costs_f64, asr_beam_lm_step_f32, asr_lm_bag_advance_f64 in
         place of asr_beam_step_f32; with use_graph_search and ASR_GRAPH_SEARCH_NATIVE=1 the graph search,
         DeviceGraphSearch, which adds asr_graph_merge_f32; None when an LM bag outgrew the cap or the
-        graph search's node store its budget, `_native_gave_up` says which): per label step the LM state of
-        the last frame as dense products (TCN.last_step), ONE launch for the local attention
-        + context (asr_tcn_attention_step_f32, or asr_tcn_attention_step_win_f32 under a
-        force_forward window), the output MLP, ONE launch for the beam
-        bookkeeping (asr_beam_step_f32) — no host read-back inside a step; the all-finished
-        flag is polled every `poll_every` steps (steps behind the flag change nothing)."""
+        graph search's node store its budget, `_native_gave_up` says which): per label step the
+        step body (_DeviceStepper.step) and ONE launch for the beam bookkeeping (asr_beam_step_f32)
+        — no host read-back inside a step; the all-finished flag is polled every `poll_every`
+        steps (steps behind the flag change nothing)."""
         from att_speech import _native
-        from att_speech.modules.beam_search import DeviceBeamSearch
         T, B, E = encoded.shape
-        beam, dev, attn = self.beam_size, encoded.device, self.attn
-        hyps = B * beam
+        beam, dev = self.beam_size, encoded.device
         lens = torch.as_tensor(encoded_lens).to(dev, torch.int32)
         self._native_gave_up = None
-        if self.lm and self.use_graph_search:
-            from att_speech.modules import beam_search as bs
-            need = bs.DeviceGraphSearch.store_bytes(B, beam, self.TRANSCRIPTION_LEN_GUARD, T)
-            if need > bs.GRAPH_STORE_BUDGET_BYTES:
-                self._native_gave_up = ('graph_store', need, bs.GRAPH_STORE_BUDGET_BYTES)
-                return None                              # refused before anything is allocated
-            search = bs.DeviceGraphSearch(
-                self.hash_dec, self.graph_search_merge_threshold, self._graph_span(),
-                self.lm, self.lm_weight, self.alphabet_mapping, self.min_attention_pos,
-                self.coverage_tau, self.coverage_weight, B, beam, dev, self.num_classes,
-                self.length_normalization, self.TRANSCRIPTION_LEN_GUARD, T, lens,
-                keep_eos_score=self.keep_eos_score)
-        elif self.lm:
-            from att_speech.modules.beam_search import DeviceBeamSearchLM
-            search = DeviceBeamSearchLM(
-                self.lm, self.lm_weight, self.alphabet_mapping, self.min_attention_pos,
-                self.coverage_tau, self.coverage_weight, B, beam, dev, self.num_classes,
-                self.length_normalization, self.TRANSCRIPTION_LEN_GUARD, T, lens,
-                keep_eos_score=self.keep_eos_score)
-        else:
-            search = DeviceBeamSearch(B, beam, dev, self.num_classes, self.length_normalization,
-                                      self.TRANSCRIPTION_LEN_GUARD)
-        # per-utterance operands (the reference repeats them per hypothesis, :449-456)
-        (eproj, _), first = attn.init_attention(encoded, lens)
-        eproj = eproj.contiguous()
-        enc = encoded.contiguous()
+        search = self._make_device_search(B, dev, lens, T)
+        if search is None:
+            return None
+        stepper = _DeviceStepper(self, encoded, lens)
+        first = stepper.first
         att = first.t().repeat_interleave(beam, dim=0).contiguous()          # [hyp, T]
-        plan = self.tcn.last_step_plan(self.tcn.eff_history)
-        w_att = torch.cat((attn.lm_to_kernel.weight, attn.lm_to_global.weight)).detach()
-        b_att = torch.cat((attn.lm_to_kernel.bias, attn.lm_to_global.bias)).detach()
-        n_filt = attn.lm_to_kernel.out_features
-        w_score = attn.hidden_to_score.weight.detach().reshape(-1).contiguous()
-        b_score = float(attn.hidden_to_score.bias)
-        history = enc.new_zeros(self.tcn.eff_history, hyps, self.tcn_hidden_size)
+        history = stepper.empty_history(B * beam)
         parent = None
-        window = tuple(attn.force_forward) if attn.force_forward else None
         trace_att = [first.repeat_interleave(beam, dim=1).detach()] if return_attention else None
         trace_logits = []
         for step in range(self.TRANSCRIPTION_LEN_GUARD):
-            lm_state = TCN.last_step(history, plan)
-            fg = torch.addmm(b_att, lm_state, w_att.t())
-            att, context = _native.tcn_attention_step(
-                eproj, enc, lens, fg[:, :n_filt].contiguous(), fg[:, n_filt:].contiguous(),
-                w_score, b_score, attn.temperature, att, parent, beam, window=window)
-            logits = self._step_output(lm_state, context)
+            logits, att = stepper.step(history, att, parent, beam)
             chosen, parent = search.step(logits, att)
             if return_attention:
                 trace_logits.append(logits.detach()[None])
                 trace_att.append(att.t().detach())
-            history = torch.cat((history[1:].index_select(1, parent.long()),
-                                 self.embedding(chosen.long())[None]))
+            history = stepper.roll(history, parent, chosen)
             if (return_attention or step % poll_every == poll_every - 1) and search.poll_finished():
                 break
         search.finalize()
@@ -591,13 +635,23 @@ class AttentionDecoderTCN(nn.Module):
             self._last_bag_overflow = search.overflow
             self._native_gave_up = ('lm_bag_overflow', search.overflow, _native.LM_BAG_CAP)
             return None                                  # an LM bag outgrew the device's cap
-        out = {'decoded': search.best_finished,
-               'decoded_scores': search.best_finished_scores_elements,
-               'loss': torch.Tensor(search.best_finished_scores).mean()}
+        return self._decode_result(search, return_attention, trace_att, trace_logits)
+
+    @staticmethod
+    def _decode_result(search, return_attention, trace_att, trace_logits):
+        out = bs.best_result(search)
         if return_attention:
             out.update(attweights=trace_att, logits=trace_logits)
         out.update(coverage=search.coverage, graph=search.get_graph(), beam_search=search)
         return out
+
+    def _warn_gave_up(self, prefix=''):
+        """the device path returned None: say why (`_native_gave_up`), once per process and key"""
+        from att_speech import _native
+        why, asked, cap = self._native_gave_up
+        if not _native._WARNED.get(prefix + why):
+            _native._WARNED[prefix + why] = True
+            warnings.warn(_GAVE_UP_WARNINGS[prefix + why] % (asked, cap))
 
     def _decode_host_each(self, encoded, encoded_lens, return_attention):
         """The host BeamSearchLM / GraphSearch takes one utterance per call: a batch whose device
@@ -633,18 +687,7 @@ class AttentionDecoderTCN(nn.Module):
             out = self._decode_native(encoded, encoded_lens, return_attention)
             if out is not None:
                 return out
-            from att_speech import _native
-            why, asked, cap = self._native_gave_up
-            if not _native._WARNED.get(why):
-                _native._WARNED[why] = True
-                if why == 'graph_store':
-                    warnings.warn('the node store of the device graph search would take %d bytes, above its '
-                                  'budget of %d: decoding this call with the host GraphSearch, one utterance '
-                                  'at a time' % (asked, cap))
-                else:
-                    warnings.warn('an LM bag of the device beam search asked for at least %d states, above '
-                                  'its cap of %d: decoding this call with the host BeamSearchLM, one utterance at a time'
-                                  % (asked, cap))
+            self._warn_gave_up()
             if encoded.size(1) > 1:
                 return self._decode_host_each(encoded, encoded_lens, return_attention)
         search = self._make_search(encoded.size(1), encoded.device)
@@ -664,13 +707,7 @@ class AttentionDecoderTCN(nn.Module):
             state['inputs'] = torch.cat((history[1:, parent], self.embedding(chosen)[None]))
             if search.has_finished():
                 break
-        out = {'decoded': search.best_finished,
-               'decoded_scores': search.best_finished_scores_elements,
-               'loss': torch.Tensor(search.best_finished_scores).mean()}
-        if return_attention:
-            out.update(attweights=trace_att, logits=trace_logits)
-        out.update(coverage=search.coverage, graph=search.get_graph(), beam_search=search)
-        return out
+        return self._decode_result(search, return_attention, trace_att, trace_logits)
 
     # ---------------------------------------------------------------- forced scoring
     def _check_sentences(self, sentences, batch_size):
@@ -701,13 +738,7 @@ class AttentionDecoderTCN(nn.Module):
                 and 1 <= encoded.size(0) <= _STEP_MAX_FRAMES and 2 <= self.num_classes <= 2048
                 and self._native_window_ok()):
             return False
-        if self.lm is not None:
-            lm = self.lm
-            if (lm.eps_rank() is None or not len(lm.ilabel)
-                    or int(lm.ilabel.max()) >= self.num_classes
-                    or lm.device_arrays(encoded.device) is None):
-                return False
-        return True
+        return self.lm is None or self._lm_fits_device(encoded)
 
     def _score_lm_host(self, sent):
         """score_lm of the scripts: the cost of the bag after the sentence and EOS"""
@@ -751,42 +782,27 @@ class AttentionDecoderTCN(nn.Module):
 
     def _score_sentences_native(self, encoded, lens, sentences):
         """The device path: the sentences of every utterance as a prefix trie, one label step per
-        trie LEVEL for all distinct prefixes of that length (the body of _decode_native with the
-        forced bookkeeping of DeviceForcedScorer in place of a search), nothing read back before the
-        end.  None when an LM bag outgrew the device's cap."""
+        trie LEVEL for all distinct prefixes of that length (_DeviceStepper.step, a level `width`
+        rows per utterance, with the forced bookkeeping of DeviceForcedScorer behind it), nothing
+        read back before the end.  None when an LM bag outgrew the device's cap."""
         from att_speech import _native
-        from att_speech.modules import beam_search as bs
         T, B, E = encoded.shape
-        dev, attn = encoded.device, self.attn
+        dev = encoded.device
         tries = [bs.sentence_trie(per_utt, self.EOS) for per_utt in sentences]
         levels, offsets = bs.batch_trie_levels(tries)
         lens_dev = torch.as_tensor(lens).to(dev, torch.int32)
         scorer = bs.DeviceForcedScorer(levels, offsets[-1], B, dev, self.num_classes, T, lens_dev,
                                        self.coverage_tau, lm=self.lm,
                                        alphabet_mapping=self.alphabet_mapping)
-        (eproj, _), first = attn.init_attention(encoded, lens_dev)
-        eproj, enc = eproj.contiguous(), encoded.contiguous()
-        att0 = first.t().contiguous()                                          # [B, T]
-        plan = self.tcn.last_step_plan(self.tcn.eff_history)
-        w_att = torch.cat((attn.lm_to_kernel.weight, attn.lm_to_global.weight)).detach()
-        b_att = torch.cat((attn.lm_to_kernel.bias, attn.lm_to_global.bias)).detach()
-        n_filt = attn.lm_to_kernel.out_features
-        w_score = attn.hidden_to_score.weight.detach().reshape(-1).contiguous()
-        b_score = float(attn.hidden_to_score.bias)
-        window = tuple(attn.force_forward) if attn.force_forward else None
-        history = enc.new_zeros(self.tcn.eff_history, B, self.tcn_hidden_size)
-        att = att0
+        stepper = _DeviceStepper(self, encoded, lens_dev)
+        att = att0 = stepper.first.t().contiguous()                            # [B, T]
+        history = stepper.empty_history(B)
         for l, lv in enumerate(levels):
             if l:
-                history = torch.cat((history[1:].index_select(1, scorer.index(l, 'parent', long=True)),
-                                     self.embedding(scorer.index(l, 'label', long=True))[None]))
-            lm_state = TCN.last_step(history, plan)
-            fg = torch.addmm(b_att, lm_state, w_att.t())
-            att, context = _native.tcn_attention_step(
-                eproj, enc, lens_dev, fg[:, :n_filt].contiguous(), fg[:, n_filt:].contiguous(),
-                w_score, b_score, attn.temperature, att, scorer.index(l, 'parent'), lv['width'],
-                window=window)
-            scorer.step(self._step_output(lm_state, context), att, att_init=att0)
+                history = stepper.roll(history, scorer.index(l, 'parent', long=True),
+                                       scorer.index(l, 'label', long=True))
+            logits, att = stepper.step(history, att, scorer.index(l, 'parent'), lv['width'])
+            scorer.step(logits, att, att_init=att0)
         acoustic, covered, lm, overflow = scorer.finish()
         if overflow:
             self._native_gave_up = ('lm_bag_overflow', overflow, _native.LM_BAG_CAP)
@@ -827,13 +843,7 @@ class AttentionDecoderTCN(nn.Module):
             if total and self._native_forced_ok(encoded):
                 parts = self._score_sentences_native(encoded, lens, sentences)
                 if parts is None:
-                    from att_speech import _native
-                    why, asked, cap = self._native_gave_up
-                    if not _native._WARNED.get('forced_' + why):
-                        _native._WARNED['forced_' + why] = True
-                        warnings.warn('an LM bag of the device forced scorer asked for at least %d '
-                                      'states, above its cap of %d: scoring this call with the host '
-                                      'loop, one sentence at a time' % (asked, cap))
+                    self._warn_gave_up('forced_')
             if parts is None:
                 parts = self._score_sentences_host(encoded, lens, sentences)
         out = []

@@ -82,7 +82,7 @@ def window_masks(att_prev, parent, lens, beam, window, mut=None):
     note('tie_in_short_row', (at_peak.sum(1) > 1) & torch.tensor(T <= 10))
     if bool((~active).any()):
         kinds.add('diffuse')
-    if parent is not None:
+    if parent is not None and len(par) == hyps:     # (rows and previous rows correspond: siblings)
         own_first = torch.where(a_all == a_all.max(1)[0][:, None], t, torch.full_like(t, T)).min(1)[0]
         elsewhere = (own_first != own_first[par]) & active
         for p in set(par.tolist()):
