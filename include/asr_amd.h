@@ -1090,6 +1090,50 @@ int asr_lattice_shared_forward_f32(
     int n_light_in, int lanes_in, float neg_inf, int viterbi, float *out_score,
     int32_t *out_best_il, void *workspace, int64_t workspace_bytes, void *stream);
 
+/*
+ * CTC forced alignment: batched Viterbi with traceback over the reference's dense CTC lattices
+ * (csrc/ctc_align.hip).  Replaces, for a whole batch in one launch, mono_CTC_viterbi_align
+ * (att_speech/modules/ctc_losses.py:475-481) and bi_CTC_viterbi_align (:505-511), i.e.
+ * raw_generic_viterbi (:412-457) with start states {0, 1} and terminal states {N-2, N-1} over the
+ * matrices of get_CTC_matrices_mono (:67-94) / get_CTC_matrices_bicontext (:111-166, without
+ * loop_using_symbol_repetitions).  The kernel reads no graph matrices: it derives the class of
+ * each of the N = 2 L + 1 states and its self-loop / skip flags from the labels.  These entry
+ * points are additions: no existing signature changes, so the ABI version stays 24.
+ *
+ *   lp         [T,B,C] f32   log-probs, time-major; must be finite (the reference itself turns a
+ *                            -inf into NaN in its emission product)
+ *   lens       [B]     i32   frames of each utterance (any order)
+ *   labels     [B,Lmax] i32  transcripts, padded; context_order 2 reduces them modulo S
+ *   label_lens [B]     i32
+ *   S                        symbols including the blank (context_order 2: S * S <= C)
+ *   context_order            1 (mono) or 2 (bicontext with contextual blanks)
+ *   allow_nonblank_selfloops, eval_repeats_in_context: the bicontext options (:111-113)
+ *   out_cost     [B]   f64   -log-prob of the best alignment; +inf when there is none
+ *   out_frames   [B,T] i32   class emitted at each frame (the reference's `sol`)
+ *   out_states   [B,T] i32   lattice state at each frame (2 i + 1 = label i, even = blanks)
+ *   out_segments [B,Lmax,2] i32  (first frame of label i, one past its last)
+ *   workspace: asr_ctc_align_workspace_bytes(T,B,Lmax) bytes (0, and NULL accepted, when the
+ *              back-pointers of an utterance, T * ceil4(ceil(N/4)) bytes, fit 48 KiB of LDS)
+ *
+ * The accumulator is fp64 and each step adds one float32 value, as in the reference; the three
+ * candidates are compared in ascending source order with a strict `>` (np.argmax: first
+ * maximum), and of the terminal states N-2 wins a tie: cost, path and ties are bit-identical to
+ * the reference.  Rows t >= lens[b] and labels i >= label_lens[b] are -1.  An utterance with no
+ * alignment (lens[b] too short for the transcript, lens[b] == 0 or > T, label_lens[b] == 0 or
+ * > Lmax, a negative label, a mono label >= C) gets cost +inf and -1 everywhere.
+ * asr_ctc_align_supported: T >= 1, 1 <= Lmax <= 511, C >= 1 (one wave holds N <= 256, four waves
+ * N <= 1023); otherwise asr_ctc_align_f64 returns ASR_EUNSUPPORTED and the caller aligns on the
+ * host.  ASR_EINVAL: null pointers, context_order outside {1, 2}, S * S > C, a workspace that is
+ * too small.  One workgroup per utterance, no atomics.
+ */
+int asr_ctc_align_supported(int T, int Lmax, int C);
+int64_t asr_ctc_align_workspace_bytes(int T, int B, int Lmax);
+int asr_ctc_align_f64(const float *lp, const int32_t *lens, const int32_t *labels,
+                      const int32_t *label_lens, int B, int T, int C, int Lmax, int S,
+                      int context_order, int allow_nonblank_selfloops, int eval_repeats_in_context,
+                      double *out_cost, int32_t *out_frames, int32_t *out_states,
+                      int32_t *out_segments, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,10 @@ _SIGNATURES = {
     'asr_gaussian_noise_f32': (_i, [_vp, _i, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, _i, _i, _vp]),
     'asr_edit_distance_max_len': (_i, []),
     'asr_edit_distance_stats_i32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'asr_ctc_align_supported': (_i, [_i, _i, _i]),
+    'asr_ctc_align_workspace_bytes': (_i64, [_i, _i, _i]),
+    'asr_ctc_align_f64': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                               _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'asr_split_bf16_f32': (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     'asr_log_softmax_shift_bwd_split_blocks': (_i, [_i64]),
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),
@@ -1503,3 +1507,36 @@ def edit_distance_stats(x, x_off, y, y_off, max_x, max_y):
                                             int(max_y), _p(out), _stream()),
           'asr_edit_distance_stats_i32')
     return out
+
+
+def ctc_align_supported(T, Lmax, C):
+    """asr_ctc_align_supported: whether asr_ctc_align_f64 is built for these shapes."""
+    return bool(lib().asr_ctc_align_supported(int(T), int(Lmax), int(C)))
+
+
+def ctc_align(lp, lens, labels, label_lens, num_symbols, context_order=1,
+              allow_nonblank_selfloops=True, eval_repeats_in_context=False):
+    """asr_ctc_align_f64: lp [T, B, C] f32 (finite), lens [B] i32, labels [B, Lmax] i32, label_lens
+    [B] i32, all on the GPU -> (cost [B] f64, frames [B, T] i32, states [B, T] i32, segments
+    [B, Lmax, 2] i32), one launch for the batch.  Shapes the kernel is not built for raise
+    NotImplementedError before anything is launched."""
+    lp = _dev(lp, torch.float32, 'log_probs')
+    lens, label_lens = _dev(lens, torch.int32, 'lens'), _dev(label_lens, torch.int32, 'label_lens')
+    labels = _dev(labels, torch.int32, 'labels')
+    T, B, C = lp.shape
+    Lmax = labels.shape[1] if labels.dim() == 2 else -1
+    if Lmax < 0 or labels.shape[0] != B or lens.numel() != B or label_lens.numel() != B:
+        raise AssertionError('ctc_align: lens [B], labels [B, Lmax] and label_lens [B] must match lp [T, B, C]')
+    L = lib()
+    dev = lp.device
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    frames = torch.empty((B, T), dtype=torch.int32, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    segments = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    nbytes = int(L.asr_ctc_align_workspace_bytes(T, B, Lmax))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    check(L.asr_ctc_align_f64(_p(lp), _p(lens), _p(labels), _p(label_lens), B, T, C, Lmax,
+                              int(num_symbols), int(context_order), int(bool(allow_nonblank_selfloops)),
+                              int(bool(eval_repeats_in_context)), _p(cost), _p(frames), _p(states),
+                              _p(segments), _p(ws), nbytes, _stream()), 'asr_ctc_align_f64')
+    return cost, frames, states, segments

@@ -57,6 +57,18 @@ class SpeechModel(nn.Module):
             enc, enc_lens = self.encoder(features, feature_lens, speakers, ivectors, **enc_kw)
             return self.decoder.decode(enc, enc_lens, texts, text_lens, spkids=speakers, **dec_kw)
 
+    def align(self, features, feature_lens, speakers, texts, text_lens,
+              encoder_args=None, decoder_args=None, ivectors=None, **kwargs):
+        """Forced alignment of the transcripts: the encoder, then decoder.align, without
+        autograd; keyword arguments as in decode.  Returns the fields of
+        ctc_viterbi_align_batch and 'alignment': per utterance (label, start, end) in
+        encoded frames."""
+        enc_kw = dict(encoder_args or {}, **kwargs)
+        dec_kw = dict(decoder_args or {}, **kwargs)
+        with torch.no_grad():
+            enc, enc_lens = self.encoder(features, feature_lens, speakers, ivectors, **enc_kw)
+            return self.decoder.align(enc, enc_lens, texts, text_lens, **dec_kw)
+
     def get_parameters_for_optimizer(self):
         return itertools.chain(self.encoder.get_parameters_for_optimizer(),
                                self.decoder.parameters())

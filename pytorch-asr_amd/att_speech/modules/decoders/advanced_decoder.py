@@ -438,6 +438,20 @@ class _ProjectionDecoder(BaseDecoder):
             ret['logits_text_diff'] = (torch.as_tensor(lens) - torch.as_tensor(text_lens)).tolist()
         return ret
 
+    def _align(self, logits, lens, texts, text_lens, context_order, **flags):
+        """ctc_viterbi_align_batch on this decoder's logits: its fields as a dict, plus
+        'alignment': per utterance the list of (label, start, end) in encoded frames."""
+        from att_speech.modules import ctc_losses
+        label_lens = [int(l) for l in torch.as_tensor(text_lens).tolist()]
+        flat = torch.cat([torch.as_tensor(t)[:l].reshape(-1).cpu().long()
+                          for t, l in zip(texts, label_lens)])
+        res = ctc_losses.ctc_viterbi_align_batch(
+            logits.detach().float(), flat, lens, label_lens,
+            num_symbols=self.num_symbols, context_order=context_order, **flags)
+        ret = dict(res._asdict())
+        ret['alignment'] = ctc_losses.alignment_spans(res, flat, label_lens)
+        return ret
+
 
 class CTCDecoderAdvanced(_ProjectionDecoder):
     """Frame-synchronous CTC decoder with a pluggable loss function and greedy
@@ -504,6 +518,23 @@ class CTCDecoderAdvanced(_ProjectionDecoder):
         return self._finish_decode(ret, 'ctc_loss', logits, encoded_lens, texts, text_lens,
                                    other_data_in_batch, return_texts_and_generated_loss,
                                    return_logits_text_diff, {})
+
+    def align(self, encoded, encoded_lens, texts, text_lens, **other):
+        """Forced alignment of the transcripts to this decoder's own logits(encoded,
+        encoded_lens), over the lattice its loss uses (context_order,
+        ctc_allow_nonblank_selfloops)."""
+        if self.loop_using_symbol_repetitions:
+            raise ValueError("align: loop_using_symbol_repetitions lattices (3 L + 1 states) are "
+                             "aligned one utterance at a time with bi_CTC_viterbi_align")
+        if self.context_order not in (1, 2):
+            raise ValueError("align: context_order %d has no dense CTC lattice" % self.context_order)
+        flags = {}
+        if self.context_order == 2:
+            flags = dict(allow_nonblank_selfloops=self.ctc_allow_nonblank_selfloops,
+                         eval_repeats_in_context=False)
+        with torch.no_grad():
+            logits = self.logits(encoded, encoded_lens)
+        return self._align(logits, encoded_lens, texts, text_lens, self.context_order, **flags)
 
     def process_sequences(self, frames, frame_lens):
         return [self.process_sequence(frames[b], frame_lens[b]) for b in range(len(frame_lens))]
@@ -683,3 +714,30 @@ class FSTDecoder(_ProjectionDecoder):
         return self._finish_decode(ret, 'fst_loss', logits, encoded_lens, texts, text_lens,
                                    other_data_in_batch, return_texts_and_generated_loss,
                                    return_logits_text_diff, None)
+
+    def align(self, encoded, encoded_lens, texts, text_lens, **other):
+        """Forced alignment of the transcripts to this decoder's own logits(encoded,
+        encoded_lens) over the training lattice of its graph generator: a CTCGraphGen of
+        context order 1, or of order 2 with contextual blanks (the dense bicontext lattice with
+        eval_repeats_in_context)."""
+        gg = self.graph_generator
+        if getattr(gg, 'grammar', None) is not None:
+            raise ValueError("align: the graph generator has a grammar FST; its numerator carries "
+                             "log G(y) and is not the plain CTC lattice")
+        if not isinstance(gg, fst_utils.CTCGraphGen):
+            raise ValueError("align: needs a CTCGraphGen, got %s" % type(gg).__name__)
+        flags = {}
+        if gg.context_order == 2:
+            args = gg.graph_build_args
+            if not args.get('use_contextual_blanks', False):
+                raise ValueError("align: a global blank (use_contextual_blanks=False) has no dense "
+                                 "bicontext lattice")
+            if not args.get('allow_nonblank_selfloops', True):
+                raise ValueError("align: without allow_nonblank_selfloops the FST lattice keeps the "
+                                 "loop of a label repeated in its own context; the dense one does not")
+            flags = dict(allow_nonblank_selfloops=True, eval_repeats_in_context=True)
+        elif gg.context_order != 1:
+            raise ValueError("align: context_order %d has no dense CTC lattice" % gg.context_order)
+        with torch.no_grad():
+            logits = self.logits(encoded, encoded_lens)
+        return self._align(logits, encoded_lens, texts, text_lens, gg.context_order, **flags)
