@@ -1134,6 +1134,68 @@ int asr_ctc_align_f64(const float *lp, const int32_t *lens, const int32_t *label
                       double *out_cost, int32_t *out_frames, int32_t *out_states,
                       int32_t *out_segments, void *workspace, int64_t workspace_bytes, void *stream);
 
+/*
+ * Beam-pruned Viterbi decoding over one shared WFST (csrc/wfst_decode.hip): the search the
+ * reference leaves to Kaldi's decode-faster over CTC_LG_syms.fst (egs/wsj/ctc_kaldi_decode.sh:144-147,
+ * --beam, --acoustic-scale, --allow-partial), batched, as frame-synchronous token passing with the
+ * order-independent semantics of DESIGN.md section 4.19.  These entry points are additions: no
+ * existing signature changes, so the ABI version stays 24.
+ *
+ *   lp            f32   log-probs: utterance b, frame t, class c at lp[t * frame_stride + b * C + c]
+ *                       (a [T,B,C] tensor has frame_stride = B * C; a chunk of the utterances of a
+ *                       larger batch keeps that batch's stride).  Frames t >= lens[b] are never read.
+ *   lens          [B] i32   frames of each utterance, 1 <= lens[b] <= T (otherwise an empty result)
+ *   the graph: tropical, N states, A arcs in CSR by source, start state `start`
+ *     arc_ptr     [N+1] u32   arcs of state s are [arc_ptr[s], arc_ptr[s+1]); "arc index" below
+ *     arc_src, arc_dst  [A] i32
+ *     arc_ilabel  [A] i32     0: non-emitting; i > 0 reads class i - 1 (decoding_utils/ctc_fst.py:42-44)
+ *     arc_olabel  [A] i32     0: no output
+ *     arc_weight  [A] f32     finite costs of any sign
+ *     final_cost  [N] f32     +inf: not final
+ *     eps_ptr [N+1] u32, eps_arc [E] u32: the arc indices of the non-emitting arcs, by source
+ *     eps_rank    [N] i32     every non-emitting arc goes from a lower to a higher rank (the
+ *                             non-emitting sub-graph is acyclic); num_ranks = 1 + the highest rank a
+ *                             non-emitting arc leaves, 0 without such arcs
+ *   beam >= 0 (+inf: no pruning), acoustic_scale, allow_partial
+ *   list_cap, log_cap: tokens one frame may hold / back-pointer records one utterance may write;
+ *     word_cap: output labels one path may carry.  An utterance that outgrows any of them gets
+ *     out_overflow[b] = 1 and no result: the caller redoes it elsewhere.  No retry on the device.
+ *   threads: 0 (512 threads per workgroup above 256 utterances, 1024 up to there: measured,
+ *     DESIGN.md section 4.19), or 256 / 512 / 1024 for timing runs
+ *   out_cost [B] f32 (+inf: no result), out_reached_final [B] i32, out_alignment [B,T] i32 (the
+ *     ilabel of the emitting arc of every frame, -1 beyond lens[b] or without a result),
+ *     out_num_active [B,T] i32 (tokens that survive the frame's last prune; the frame lens[b] - 1 is
+ *     not pruned), out_words [B,word_cap] i32 with out_num_words [B]: the olabels != 0 along the
+ *     path, LAST word first.
+ *   workspace: asr_wfst_decode_workspace_bytes(N, B, list_cap, log_cap) bytes = per utterance
+ *     12 N + 20 list_cap + 8 log_cap, rounded; the caller splits a batch whose tables exceed its budget.
+ *
+ * Arithmetic (all fp32, one rounding per operation, no contraction): a = -(acoustic_scale * lp);
+ * an emitting arc proposes (c(src) + w) + a[ilabel] to its destination, a non-emitting arc
+ * c(src) + w, in rank order; a state's cost is the minimum of its proposals and the smallest arc
+ * index wins among equal ones, whether emitting or not; survivors satisfy c <= min c + beam, after
+ * the emitting phase and again after the closure; the answer is argmin c + final over the final
+ * states reached after the last frame (ties: the smallest state id), else with allow_partial
+ * argmin c.  asr_wfst_decode_supported: 1 <= N < 2^31, A < 2^32 - 1, 1 <= C <= 4096, T >= 1;
+ * otherwise ASR_EUNSUPPORTED.  ASR_EINVAL: null pointers, start outside the graph, a negative or NaN
+ * beam, capacities outside [1, 2^31), threads outside {0, 256, 512, 1024}, a workspace that is too small.  One workgroup per
+ * utterance, workgroup barriers only; every loop is bounded by lens, num_ranks, the capacities
+ * and the arc counts, and out-of-range indices of a broken graph are skipped.
+ */
+int asr_wfst_decode_supported(int64_t N, int64_t A, int C, int T);
+int64_t asr_wfst_decode_workspace_bytes(int64_t N, int B, int64_t list_cap, int64_t log_cap);
+int asr_wfst_decode_f32(const float *lp, int64_t frame_stride, const int32_t *lens, int T, int B, int C,
+                        int64_t N, int64_t A, const uint32_t *arc_ptr, const int32_t *arc_src,
+                        const int32_t *arc_dst, const int32_t *arc_ilabel, const int32_t *arc_olabel,
+                        const float *arc_weight, const float *final_cost, const uint32_t *eps_ptr,
+                        const uint32_t *eps_arc, int64_t E, const int32_t *eps_rank, int num_ranks,
+                        int start, float beam, float acoustic_scale, int allow_partial, int64_t list_cap,
+                        int64_t log_cap, int word_cap, int threads, float *out_cost,
+                        int32_t *out_reached_final,
+                        int32_t *out_alignment, int32_t *out_num_active, int32_t *out_words,
+                        int32_t *out_num_words, int32_t *out_overflow, void *workspace,
+                        int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

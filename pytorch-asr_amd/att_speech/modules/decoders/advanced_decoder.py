@@ -602,8 +602,12 @@ class FSTDecoder(_ProjectionDecoder):
     def __init__(self, sample_batch, num_classes,
                  graph_generator, normalize_by_dim=None,
                  numerator_red='logsumexp', denominator_red='logsumexp',
-                 embedder='LutLinear', embedder_kwargs={}, **kwargs):
+                 embedder='LutLinear', embedder_kwargs={}, decode_beam=None, **kwargs):
         super(FSTDecoder, self).__init__(**kwargs)
+        # decode_beam: None = the exact every-state Viterbi below; a number = the beam-pruned
+        # token-passing search (att_speech/wfst_decode.py) over the same graph with that beam
+        self.decode_beam = decode_beam
+        self._decoding_graph = None
         gg = utils.contruct_from_kwargs(
             graph_generator, 'att_speech.fst_utils',
             {'num_classes': num_classes, 'num_symbols': self.num_symbols})
@@ -703,6 +707,16 @@ class FSTDecoder(_ProjectionDecoder):
                **other_data_in_batch):
         logits = self.logits(encoded, encoded_lens)
         gg = self.graph_generator
+        if self.decode_beam is not None:
+            from att_speech import wfst_decode
+            if self._decoding_graph is None:
+                self._decoding_graph = wfst_decode.DecodingGraph.from_graph_generator(gg)
+            res = wfst_decode.decode_graph(logits.detach().float(), encoded_lens, self._decoding_graph,
+                                           beam=float(self.decode_beam))
+            ret = {'decoded': res['words'], 'logits': logits}   # the labels on the winning arcs
+            return self._finish_decode(ret, 'fst_loss', logits, encoded_lens, texts, text_lens,
+                                       other_data_in_batch, return_texts_and_generated_loss,
+                                       return_logits_text_diff, None)
         # best state sequence; the reference reads the same indices off the autograd
         # gradient of the Viterbi score (:546-554)
         states = fst_utils.viterbi_path(logits.detach(), encoded_lens,
