@@ -1196,6 +1196,56 @@ int asr_wfst_decode_f32(const float *lp, int64_t frame_stride, const int32_t *le
                         int32_t *out_num_words, int32_t *out_overflow, void *workspace,
                         int64_t workspace_bytes, void *stream);
 
+/*
+ * Lattice generation from the same search (csrc/wfst_lattice.hip): where the reference runs
+ * decode-faster once per acoustic scale (egs/wsj/ctc_kaldi_decode.sh:160-163), one search keeps
+ * every arc within lattice_beam of the best path, graph cost and acoustic score apart
+ * (latgen-faster), with the order-independent semantics of DESIGN.md section 4.20.  Additions
+ * again: the ABI version stays 24.
+ *
+ * lp, lens, the graph, beam, acoustic_scale, allow_partial, list_cap, log_cap, threads: as for
+ * asr_wfst_decode_f32 (arc_olabel is not read).  The forward IS that search: out_cost and
+ * out_reached_final are the same bits.
+ *   lattice_beam >= 0 (+inf: every arc with a finite value)
+ *   node_cap, arc_cap: nodes / arcs one utterance may keep
+ *   out_overflow [B] i32: 0, or which capacity the utterance outgrew (1 a token list, 2 the log,
+ *     3 node_cap, 4 arc_cap); it then has no result and the caller redoes it elsewhere
+ *   out_num_nodes, out_num_arcs [B] i32 (0 nodes: no lattice, out_cost = +inf)
+ *   node_time, node_state [B,node_cap] i32, node_alpha, node_beta [B,node_cap] f32
+ *   lat_src, lat_dst [B,arc_cap] i32 (node indices of the utterance), lat_arc [B,arc_cap] u32
+ *     (arc index in the graph), lat_lp [B,arc_cap] f32 (the class score read, unscaled; 0 for
+ *     non-emitting arcs).  Nodes and arcs come in no particular order: the caller sorts.
+ *   workspace: asr_wfst_lattice_workspace_bytes(N, B, T, list_cap, log_cap) bytes = per utterance
+ *     12 N + 20 list_cap + 24 log_cap + 8 (T + 2), rounded.
+ *
+ * Time k = frames consumed.  A node is a token (k, state) that exists after the closure at time k,
+ * alpha its cost.  Lattice arcs: emitting arcs from the survivors of time k - 1 whose proposal
+ * (alpha + w) + a[ilabel] is finite and within the threshold of frame k's first prune;
+ * non-emitting arcs between tokens of one time with alpha + w finite.  beta: final cost at time
+ * lens[b] (0 everywhere when no final state was reached and allow_partial is set), and backwards
+ * beta(u) = min over the lattice arcs u -> v of x + beta(v), x = w + a[ilabel] (w for non-emitting
+ * arcs), through a 32-bit atomic minimum over the order-preserving key.  Kept: the arcs with
+ * alpha(u) + (x + beta(v)) finite and <= out_cost + lattice_beam, and the arcs of the search's own
+ * traceback; the nodes are their end points and the start token.  All fp32, one rounding per
+ * operation.  One workgroup per utterance does forward and backward in one launch, workgroup
+ * barriers only; every loop is bounded by lens, num_ranks, the capacities and the arc counts.
+ */
+int asr_wfst_lattice_supported(int64_t N, int64_t A, int C, int T);
+int64_t asr_wfst_lattice_workspace_bytes(int64_t N, int B, int T, int64_t list_cap, int64_t log_cap);
+int asr_wfst_lattice_f32(const float *lp, int64_t frame_stride, const int32_t *lens, int T, int B, int C,
+                         int64_t N, int64_t A, const uint32_t *arc_ptr, const int32_t *arc_src,
+                         const int32_t *arc_dst, const int32_t *arc_ilabel, const int32_t *arc_olabel,
+                         const float *arc_weight, const float *final_cost, const uint32_t *eps_ptr,
+                         const uint32_t *eps_arc, int64_t E, const int32_t *eps_rank, int num_ranks,
+                         int start, float beam, float lattice_beam, float acoustic_scale,
+                         int allow_partial, int64_t list_cap, int64_t log_cap, int64_t node_cap,
+                         int64_t arc_cap, int threads, float *out_cost, int32_t *out_reached_final,
+                         int32_t *out_num_nodes, int32_t *out_num_arcs, int32_t *node_time,
+                         int32_t *node_state, float *node_alpha, float *node_beta,
+                         int32_t *lat_src, int32_t *lat_dst, uint32_t *lat_arc, float *lat_lp,
+                         int32_t *out_overflow, void *workspace, int64_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

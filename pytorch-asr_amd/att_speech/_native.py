@@ -82,6 +82,10 @@ _SIGNATURES = {
     'asr_wfst_decode_workspace_bytes': (_i64, [_i64, _i, _i64, _i64]),
     'asr_wfst_decode_f32': (_i, [_vp, _i64, _vp, _i, _i, _i, _i64, _i64] + [_vp] * 9 + [_i64, _vp, _i, _i,
                                  _f, _f, _i, _i64, _i64, _i, _i] + [_vp] * 8 + [_i64, _vp]),
+    'asr_wfst_lattice_supported': (_i, [_i64, _i64, _i, _i]),
+    'asr_wfst_lattice_workspace_bytes': (_i64, [_i64, _i, _i, _i64, _i64]),
+    'asr_wfst_lattice_f32': (_i, [_vp, _i64, _vp, _i, _i, _i, _i64, _i64] + [_vp] * 9 + [_i64, _vp, _i, _i,
+                                  _f, _f, _f, _i, _i64, _i64, _i64, _i64, _i] + [_vp] * 14 + [_i64, _vp]),
     'asr_split_bf16_f32': (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     'asr_log_softmax_shift_bwd_split_blocks': (_i, [_i64]),
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),

@@ -602,11 +602,18 @@ class FSTDecoder(_ProjectionDecoder):
     def __init__(self, sample_batch, num_classes,
                  graph_generator, normalize_by_dim=None,
                  numerator_red='logsumexp', denominator_red='logsumexp',
-                 embedder='LutLinear', embedder_kwargs={}, decode_beam=None, **kwargs):
+                 embedder='LutLinear', embedder_kwargs={}, decode_beam=None,
+                 decode_lattice_beam=None, decode_nbest=1, **kwargs):
         super(FSTDecoder, self).__init__(**kwargs)
         # decode_beam: None = the exact every-state Viterbi below; a number = the beam-pruned
         # token-passing search (att_speech/wfst_decode.py) over the same graph with that beam
+        # decode_lattice_beam: None = the 1-best search alone; a number = one lattice search
+        # (att_speech/wfst_lattice.py) with that lattice beam, and decode() adds 'nbest': per
+        # utterance the decode_nbest cheapest distinct label sequences as (labels, cost)
+        if decode_lattice_beam is not None and decode_beam is None:
+            raise ValueError("decode_lattice_beam needs decode_beam: the lattice comes from the beam search")
         self.decode_beam = decode_beam
+        self.decode_lattice_beam, self.decode_nbest = decode_lattice_beam, int(decode_nbest)
         self._decoding_graph = None
         gg = utils.contruct_from_kwargs(
             graph_generator, 'att_speech.fst_utils',
@@ -714,6 +721,12 @@ class FSTDecoder(_ProjectionDecoder):
             res = wfst_decode.decode_graph(logits.detach().float(), encoded_lens, self._decoding_graph,
                                            beam=float(self.decode_beam))
             ret = {'decoded': res['words'], 'logits': logits}   # the labels on the winning arcs
+            if self.decode_lattice_beam is not None:
+                from att_speech import wfst_lattice
+                lats, _ = wfst_lattice.decode_lattice(
+                    logits.detach().float(), encoded_lens, self._decoding_graph, beam=float(self.decode_beam),
+                    lattice_beam=float(self.decode_lattice_beam))
+                ret['nbest'] = [lat.nbest(self.decode_nbest) for lat in lats]
             return self._finish_decode(ret, 'fst_loss', logits, encoded_lens, texts, text_lens,
                                        other_data_in_batch, return_texts_and_generated_loss,
                                        return_logits_text_diff, None)

@@ -1,0 +1,641 @@
+"""Word lattices and n-best lists from the beam-pruned WFST search.
+
+`decode_lattice` runs the search of att_speech.wfst_decode.decode_graph once and keeps, next to
+the best path, every arc that lies within `lattice_beam` of it, with graph cost and acoustic score
+apart on every arc: Kaldi's latgen-faster where the recipe ran decode-faster once per acoustic
+scale (egs/wsj/ctc_kaldi_decode.sh:160-163).  A `Lattice` is re-ranked on the host
+(`best_path(acoustic_scale=...)`: lattice-best-path) and listed (`nbest`: lattice-to-nbest), and
+`sentences` has the shape AttentionDecoderTCN.score_sentences takes.
+
+Semantics (order-independent, so the device kernel asr_wfst_lattice_f32,
+the host path below and the tests' fp64 referee agree bit for bit).  The search is section 4.19's.
+Time k = frames consumed; V_k the tokens after the closure at time k with costs alpha, S_k those
+that survive the prune (S_n = V_n), thr_k the threshold of frame k's emitting phase.
+
+  lattice arcs   emitting (k-1, s) -> (k, d): s in S_{k-1} and the proposal (alpha + w) + a_k[il]
+                 is finite and <= thr_k; epsilon (k, s) -> (k, d): s, d in V_k, alpha + w finite
+  beta           beta(n, s) = final(s) when a final state was reached, else 0 (allow_partial);
+                 beta(u) = min over the lattice arcs u -> v of x + beta(v), x = w + a_k[il]
+                 (w for epsilon arcs), fp32, one rounding per operation
+  kept           alpha(u) + (x + beta(v)) <= best + lattice_beam (and finite), plus the arcs of
+                 the search's own traceback
+"""
+import heapq
+import os
+import warnings
+
+import numpy as np
+import torch
+
+from att_speech import _native
+from att_speech.wfst_decode import DEFAULT_WORKSPACE_BYTES, _NOARC, _closure, _merge, _ranges
+
+INF = float('inf')
+DEFAULT_MAX_EXPANSIONS = 1 << 20
+
+OVERFLOW_NAMES = {1: 'list', 2: 'log', 3: 'nodes', 4: 'arcs'}
+
+
+class Lattice(object):
+    """One utterance's pruned lattice in canonical form.
+
+    Nodes sorted by (time, state): time, state [n_nodes] int32, alpha, beta [n_nodes] float32.
+    Arcs sorted by (src node, graph arc index): src, dst (node indices), arc (the CSR position in
+    `graph`) [n_arcs] int32/int64 and lp [n_arcs] float32, the raw class score the arc read (0 for
+    epsilon arcs).  cost: the search's answer (+inf and no nodes: no lattice); reached_final: the
+    end nodes are the final states of time num_frames (else every node of that time, cost 0)."""
+
+    def __init__(self, graph, acoustic_scale, num_frames, cost, reached_final, time, state, alpha, beta,
+                 src, dst, arc, lp):
+        self.graph, self.acoustic_scale, self.num_frames = graph, float(acoustic_scale), int(num_frames)
+        self.cost, self.reached_final = np.float32(cost), bool(reached_final)
+        self.time, self.state = np.asarray(time, np.int32), np.asarray(state, np.int32)
+        self.alpha, self.beta = np.asarray(alpha, np.float32), np.asarray(beta, np.float32)
+        self.src, self.dst = np.asarray(src, np.int32), np.asarray(dst, np.int32)
+        self.arc, self.lp = np.asarray(arc, np.int64), np.asarray(lp, np.float32)
+
+    FIELDS = ('time', 'state', 'alpha', 'beta', 'src', 'dst', 'arc', 'lp')
+
+    @property
+    def num_nodes(self):
+        return len(self.time)
+
+    @property
+    def num_arcs(self):
+        return len(self.arc)
+
+    @property
+    def ilabel(self):
+        return self.graph.ilabel[self.arc]
+
+    @property
+    def olabel(self):
+        return self.graph.olabel[self.arc]
+
+    @property
+    def w(self):
+        return self.graph.weight[self.arc]
+
+    # ---- fp64 dynamic programmes over the DAG ---------------------------------------
+    def _levels(self):
+        """arc index groups by the (time, epsilon rank) of the source node, ascending"""
+        R = self.graph.num_ranks + 1
+        key = self.time[self.src].astype(np.int64) * R + self.graph.rank[self.state[self.src]]
+        order = np.argsort(key, kind='stable')
+        cuts = np.nonzero(np.r_[True, key[order][1:] != key[order][:-1]])[0] if len(order) else []
+        return [order[a:b] for a, b in zip(cuts, list(cuts[1:]) + [len(order)])]
+
+    def _arc_costs(self, acoustic_scale, lm_scale):
+        sc = self.acoustic_scale if acoustic_scale is None else float(acoustic_scale)
+        return float(lm_scale) * self.w.astype(np.float64) - sc * self.lp.astype(np.float64)
+
+    def _end_costs(self, lm_scale):
+        """per node: the cost of stopping there (+inf: not an end node)"""
+        end = np.full(self.num_nodes, INF)
+        at_n = self.time == self.num_frames
+        if self.reached_final:
+            end[at_n] = float(lm_scale) * self.graph.final[self.state[at_n]].astype(np.float64)
+        else:
+            end[at_n] = 0.0
+        return end
+
+    def best_path(self, acoustic_scale=None, lm_scale=1.0):
+        """(words, cost, graph_cost, acoustic_cost) of the cheapest path when an arc costs
+        lm_scale * w - acoustic_scale * lp and a final state lm_scale * final;
+        cost = lm_scale * graph_cost + acoustic_scale * acoustic_cost.  acoustic_scale None: the
+        scale of the search.  Equal costs: the smallest arc index into a node, then the smallest
+        end state, as in the search.  No lattice: ([], inf, inf, inf)."""
+        return LatticeBatch([self]).best_paths(acoustic_scale, lm_scale)[0]
+
+    def nbest(self, n, acoustic_scale=None, lm_scale=1.0, max_expansions=DEFAULT_MAX_EXPANSIONS):
+        """The n cheapest DISTINCT word sequences as [(words, cost)], sorted by (cost, words).
+
+        Best-first over (node, word prefix) with the exact cost-to-go as the heuristic: all
+        alignments of one word sequence meet in one search state, so each sequence comes out once,
+        at its cheapest.  Sequences that tie at the n-th cost are all popped before the list is
+        cut by (cost, words).  More than max_expansions pops raise RuntimeError."""
+        n = int(n)
+        if n < 1 or not self.num_nodes:
+            return []
+        x = self._arc_costs(acoustic_scale, lm_scale)
+        end = self._end_costs(lm_scale)
+        h = end.copy()
+        for lv in reversed(self._levels()):
+            cand = x[lv] + h[self.dst[lv]]
+            ok = cand < INF
+            np.minimum.at(h, self.src[lv][ok], cand[ok])
+        start = np.nonzero((self.time == 0) & (self.state == self.graph.start))[0]
+        if not len(start) or not h[start[0]] < INF:
+            return []
+        ptr = np.searchsorted(self.src, np.arange(self.num_nodes + 1))
+        ol = self.olabel
+        END = -1
+        s0 = int(start[0])
+        heap = [(float(h[s0]), (), s0, 0.0)]
+        best_g = {(s0, ()): 0.0}
+        done = set()
+        out = []
+        pops = 0
+        while heap:
+            f, words, v, gcost = heapq.heappop(heap)
+            if (v, words) in done or gcost > best_g.get((v, words), INF):
+                continue
+            if len(out) >= n and f > out[-1][1]:
+                break
+            pops += 1
+            if pops > max_expansions:
+                raise RuntimeError("nbest: more than max_expansions = %d search states expanded for n = %d; "
+                                   "raise max_expansions or lower n / lattice_beam" % (max_expansions, n))
+            done.add((v, words))
+            if v == END:
+                out.append((list(words), gcost))
+                continue
+            if end[v] < INF:
+                c = gcost + float(end[v])
+                if c < best_g.get((END, words), INF):
+                    best_g[(END, words)] = c
+                    heapq.heappush(heap, (c, words, END, c))
+            for j in range(int(ptr[v]), int(ptr[v + 1])):
+                d = int(self.dst[j])
+                if not h[d] < INF:
+                    continue
+                c = gcost + float(x[j])
+                wd = words + (int(ol[j]),) if ol[j] != 0 else words
+                if c < best_g.get((d, wd), INF):
+                    best_g[(d, wd)] = c
+                    heapq.heappush(heap, (c + float(h[d]), wd, d, c))
+        out.sort(key=lambda e: (e[1], e[0]))
+        return out[:n]
+
+    def sentences(self, n, **kw):
+        """the word lists of nbest(n), the shape AttentionDecoderTCN.score_sentences takes"""
+        return [w for w, _ in self.nbest(n, **kw)]
+
+
+class LatticeBatch(object):
+    """The lattices of many utterances over one graph, laid end to end, so that one dynamic
+    programme serves them all: a sweep over acoustic scales builds this once and calls best_paths
+    once per scale."""
+
+    def __init__(self, lattices):
+        self.lattices = lats = list(lattices)
+        if not lats:
+            return
+        g = self.graph = lats[0].graph
+        nn = np.array([l.num_nodes for l in lats], np.int64)
+        na = np.array([l.num_arcs for l in lats], np.int64)
+        self.node_off = np.r_[0, np.cumsum(nn)]
+        self.n_utt = np.repeat(np.arange(len(lats)), nn)
+        a_utt = np.repeat(np.arange(len(lats)), na)
+        cat = np.concatenate
+        self.time, self.state = cat([l.time for l in lats]).astype(np.int64), cat([l.state for l in lats])
+        self.src = cat([l.src for l in lats]).astype(np.int64) + self.node_off[a_utt]
+        self.dst = cat([l.dst for l in lats]).astype(np.int64) + self.node_off[a_utt]
+        self.arc, self.lp = cat([l.arc for l in lats]), cat([l.lp for l in lats]).astype(np.float64)
+        self.w = g.weight[self.arc].astype(np.float64)
+        self.ol = g.olabel[self.arc]
+        self.scale = cat([np.full(k, l.acoustic_scale) for k, l in zip(na, lats)]) if len(lats) else None
+        self.start = (self.time == 0) & (self.state == g.start)
+        frames = np.array([l.num_frames for l in lats], np.int64)
+        reached = np.array([l.reached_final for l in lats], bool)
+        at_n = self.time == frames[self.n_utt]
+        # the unscaled cost of stopping at a node (+inf: not an end node)
+        self.end = np.where(at_n, np.where(reached[self.n_utt], g.final[self.state].astype(np.float64), 0.0), INF)
+        # arcs grouped by the (time, epsilon rank) of their source, ascending: a node's cost is final
+        # before its arcs are relaxed
+        key = self.time[self.src] * (g.num_ranks + 1) + g.rank[self.state[self.src]]
+        order = np.argsort(key, kind='stable')
+        cuts = np.nonzero(np.r_[True, key[order][1:] != key[order][:-1]])[0] if len(order) else []
+        # within a level the arcs are grouped by destination, so a level is one minimum.reduceat
+        self.levels = []
+        for a, b in zip(cuts, list(cuts[1:]) + [len(order)]):
+            lv = order[a:b]
+            lv = lv[np.argsort(self.dst[lv], kind='stable')]
+            d = self.dst[lv]
+            first = np.nonzero(np.r_[True, d[1:] != d[:-1]])[0]
+            self.levels.append((lv, self.src[lv], first, d[first]))
+
+    def best_paths(self, acoustic_scale=None, lm_scale=1.0):
+        """Lattice.best_path for every lattice: a list of (words, cost, graph_cost, acoustic_cost)"""
+        none = ([], INF, INF, INF)
+        if not self.lattices:
+            return []
+        B, N = len(self.lattices), len(self.time)
+        if not N:
+            return [none] * B
+        sc = self.scale if acoustic_scale is None else float(acoustic_scale)
+        x = float(lm_scale) * self.w - sc * self.lp
+        cost = np.where(self.start, 0.0, INF)
+        for lv, src, first, dst in self.levels:
+            cost[dst] = np.minimum(cost[dst], np.minimum.reduceat(cost[src] + x[lv], first))
+        cand = cost[self.src] + x
+        win = np.nonzero((cand == cost[self.dst]) & (cand < INF))[0]
+        # of the arcs that attain a node's cost, the smallest GRAPH arc index (not lattice position)
+        garc = np.full(N, np.iinfo(np.int64).max, np.int64)
+        np.minimum.at(garc, self.dst[win], self.arc[win])
+        hit = win[self.arc[win] == garc[self.dst[win]]]
+        bp = np.full(N, -1, np.int64)
+        bp[self.dst[hit]] = hit
+        bp[self.start] = -1
+        tot = cost + float(lm_scale) * self.end
+        best = np.full(B, INF)
+        np.minimum.at(best, self.n_utt, tot)
+        # the first node that attains it: nodes are sorted by state within a time
+        v = np.full(B, N, np.int64)
+        at = np.nonzero((tot == best[self.n_utt]) & (tot < INF))[0]
+        np.minimum.at(v, self.n_utt[at], at)
+        live = v < N
+        gc = np.zeros(B)
+        gc[live] = np.where(self.end[v[live]] < INF, self.end[v[live]], 0.0)
+        ac = np.zeros(B)
+        cur = np.where(live, v, 0)
+        w_utt, w_lab, w_step = [], [], []
+        for step in range(len(self.levels) + 1):       # a path has at most one arc per level
+            j = np.where(live, bp[cur], -1)
+            live = j >= 0
+            if not live.any():
+                break
+            u = np.nonzero(live)[0]
+            ju = j[u]
+            gc[u] += self.w[ju]
+            ac[u] -= self.lp[ju]
+            has = self.ol[ju] != 0
+            w_utt.append(u[has])
+            w_lab.append(self.ol[ju][has])
+            w_step.append(np.full(int(has.sum()), step))
+            cur[u] = self.src[ju]
+        words = [[] for _ in range(B)]
+        if w_utt:
+            wu, wl, ws = np.concatenate(w_utt), np.concatenate(w_lab), np.concatenate(w_step)
+            for i in np.lexsort((-ws, wu)):             # per utterance, the last step first: path order
+                words[wu[i]].append(int(wl[i]))
+        return [(words[b], float(best[b]), float(gc[b]), float(ac[b])) if best[b] < INF else none
+                for b in range(B)]
+
+
+def best_paths(lattices, acoustic_scale=None, lm_scale=1.0):
+    """Lattice.best_path of many lattices over one graph in one dynamic programme"""
+    return LatticeBatch(lattices).best_paths(acoustic_scale, lm_scale)
+
+
+def _empty(graph, scale, n):
+    z = np.zeros(0, np.int32)
+    f = np.zeros(0, np.float32)
+    return Lattice(graph, scale, n, INF, False, z, z, f, f, z, z, z, f)
+
+
+# ----------------------------------------------------------------------------------
+# host path: numpy float32 arithmetic, the same operations as the kernel
+# ----------------------------------------------------------------------------------
+def _min_at(beta, owner, q):
+    ok = q < INF
+    np.minimum.at(beta, owner[ok], q[ok])
+
+
+def _host_one(g, lp, n, beam, lattice_beam, scale, allow_partial, cost, arcof):
+    """one utterance: lp [T, C] float32; cost / arcof as in wfst_decode._host_one.
+    Returns (Lattice, stats)."""
+    stats = dict(peak_emit=0, peak_closure=0, records=0, nodes=0, arcs=0)
+    T = lp.shape[0]
+    if n < 1 or n > T:
+        return _empty(g, scale, n), stats
+    beam, f_scale, zero = np.float32(beam), np.float32(scale), np.float32(0)
+    cost[g.start], arcof[g.start] = 0.0, _NOARC
+    act = np.array([g.start], np.int64)
+    frames, thr = [], [np.float32(np.nan)]
+    cur_s = cur_c = None
+    for t in range(-1, n):
+        if t >= 0:
+            a_sc = -(f_scale * lp[t])
+            arcs, owner = _ranges(g.ptr[cur_s], g.ptr[cur_s + 1])
+            em = g.ilabel[arcs] > 0
+            arcs, owner = arcs[em], owner[em]
+            c = (cur_c[owner] + g.weight[arcs]) + a_sc[g.ilabel[arcs] - 1]
+            act = _merge(g, cost, arcof, np.zeros(0, np.int64), arcs, c)
+            stats['peak_emit'] = max(stats['peak_emit'], len(act))
+            th = np.float32(cost[act].min() + beam) if len(act) else np.float32(np.nan)
+            thr.append(th)
+            drop = act[~(cost[act] <= th)]
+            cost[drop] = INF
+            arcof[drop] = _NOARC
+            act = act[cost[act] <= th]
+        act = _closure(g, cost, arcof, act)
+        stats['peak_closure'] = max(stats['peak_closure'], len(act))
+        stats['records'] += len(act)
+        V = np.sort(act)
+        al, ar = cost[V].copy(), arcof[V].copy()
+        surv = al <= al.min() + beam if (t < n - 1 and len(V)) else np.ones(len(V), bool)
+        frames.append((V, al, ar, surv))
+        cur_s, cur_c = V[surv], al[surv]
+        cost[act] = INF
+        arcof[act] = _NOARC
+    V, al, _, _ = frames[n]
+    if not len(V):
+        return _empty(g, scale, n), stats
+    tot = (al + g.final[V]) + zero
+    ok = tot < INF
+    reached = bool(ok.any())
+    if reached:
+        best = tot[ok].min()
+        s = int(V[ok][tot[ok] == best].min())
+    elif allow_partial:
+        best = al.min()
+        s = int(V[al == best].min())
+    else:
+        return _empty(g, scale, n), stats
+    # the arcs of the search's own traceback, by the time of their source
+    forced = [[] for _ in range(n + 1)]
+    k = n
+    while True:
+        Vk, _, ark, _ = frames[k]
+        a = int(ark[np.searchsorted(Vk, s)])
+        if a == _NOARC:
+            break
+        if g.ilabel[a] > 0:
+            k -= 1
+        forced[k].append(a)
+        s = int(g.src[a])
+    limit = np.float32(best) + np.float32(lattice_beam)
+    betas = [None] * (n + 1)
+    base = np.cumsum([0] + [len(f[0]) for f in frames])
+    k_src, k_dst, k_arc, k_lp = [], [], [], []
+
+    def keep(k, owner, kd, pos, arcs, q, alpha, scores):
+        val = alpha[owner] + q
+        m = ((val < INF) & (val <= limit)) | np.isin(arcs, forced[k])
+        k_src.append(base[k] + owner[m])
+        k_dst.append(base[kd] + pos[m])
+        k_arc.append(arcs[m])
+        k_lp.append(scores[m] if scores is not None else np.zeros(int(m.sum()), np.float32))
+
+    for k in range(n, -1, -1):
+        V, al, _, surv = frames[k]
+        if k == n:
+            beta = (g.final[V] + zero) if reached else np.zeros(len(V), np.float32)
+        else:
+            beta = np.full(len(V), INF, np.float32)
+            Vn = frames[k + 1][0]
+            a_sc = -(f_scale * lp[k])
+            idx = np.nonzero(surv)[0]
+            arcs, owner = _ranges(g.ptr[V[idx]], g.ptr[V[idx] + 1])
+            owner = idx[owner]
+            em = g.ilabel[arcs] > 0
+            arcs, owner = arcs[em], owner[em]
+            cls = g.ilabel[arcs] - 1
+            p = ((al[owner] + g.weight[arcs]) + a_sc[cls]) + zero
+            m = (p < INF) & (p <= thr[k + 1])
+            arcs, owner, cls = arcs[m], owner[m], cls[m]
+            pos = np.searchsorted(Vn, g.dst[arcs])
+            q = ((g.weight[arcs] + a_sc[cls]) + betas[k + 1][pos]) + zero
+            _min_at(beta, owner, q)
+            keep(k, owner, k + 1, pos, arcs, q, al, lp[k][cls])
+        for r in range(g.num_ranks - 1, -1, -1):
+            idx = np.nonzero((g.rank[V] == r) & (g.eps_ptr[V + 1] > g.eps_ptr[V]))[0]
+            if not len(idx):
+                continue
+            e, owner = _ranges(g.eps_ptr[V[idx]], g.eps_ptr[V[idx] + 1])
+            owner = idx[owner]
+            arcs = g.eps_arc[e]
+            d = g.dst[arcs]
+            pos = np.minimum(np.searchsorted(V, d), len(V) - 1)
+            m = (V[pos] == d) & (((al[owner] + g.weight[arcs]) + zero) < INF)
+            arcs, owner, pos = arcs[m], owner[m], pos[m]
+            q = (g.weight[arcs] + beta[pos]) + zero
+            _min_at(beta, owner, q)
+            keep(k, owner, k, pos, arcs, q, al, None)
+        betas[k] = beta
+    src = np.concatenate(k_src).astype(np.int64)
+    dst = np.concatenate(k_dst).astype(np.int64)
+    arc = np.concatenate(k_arc).astype(np.int64)
+    alp = np.concatenate(k_lp).astype(np.float32)
+    used = np.zeros(base[-1], bool)
+    used[src] = True
+    used[dst] = True
+    used[base[0] + np.searchsorted(frames[0][0], g.start)] = True
+    new_id = np.cumsum(used) - 1                   # records are ordered by (time, state) already
+    order = np.lexsort((arc, new_id[src]))
+    times = np.repeat(np.arange(n + 1), [len(f[0]) for f in frames])
+    stats['nodes'], stats['arcs'] = int(used.sum()), len(arc)
+    lat = Lattice(g, scale, n, best, reached, times[used], np.concatenate([f[0] for f in frames])[used],
+                  np.concatenate([f[1] for f in frames])[used], np.concatenate(betas)[used],
+                  new_id[src][order], new_id[dst][order], arc[order], alp[order])
+    return lat, stats
+
+
+def decode_lattice_host(lp, lens, graph, beam=16.0, lattice_beam=8.0, acoustic_scale=1.0, allow_partial=True):
+    """The host path on numpy arrays: lp [T,B,C] float32.  Returns (lattices, stats): per utterance
+    what a device run needs of its capacities (peak_emit / peak_closure against list_cap, records
+    against log_cap, nodes against node_cap, arcs against arc_cap)."""
+    lp = np.asarray(lp, np.float32)
+    B = lp.shape[1]
+    cost = np.full(graph.num_states, INF, np.float32)
+    arcof = np.full(graph.num_states, _NOARC, np.int64)
+    lats, stats = [], []
+    with np.errstate(invalid='ignore', over='ignore'):
+        for b in range(B):
+            lat, st = _host_one(graph, lp[:, b], int(lens[b]), beam, lattice_beam, acoustic_scale,
+                                allow_partial, cost, arcof)
+            lats.append(lat)
+            stats.append(st)
+    return lats, stats
+
+
+# ----------------------------------------------------------------------------------
+# device path
+# ----------------------------------------------------------------------------------
+def plan_workspace(num_states, T, B, workspace_bytes, num_arcs=None):
+    """(utterances per launch, list_cap, log_cap, node_cap, arc_cap) for a workspace budget.
+
+    wfst_decode.plan_workspace's scheme with the lattice's sizes: a record of the log takes 24 bytes
+    (arc, source record, state, alpha, beta, marks) where the 1-best search takes 8, and per
+    utterance there are 8 (T + 2) bytes of per-time offsets and thresholds.  The budget also
+    covers what comes back: 16 bytes a kept node, 16 bytes a kept arc.  When it holds a quarter of
+    the batch at the sizes that cannot overflow (a node per state and time, every graph arc at
+    every time; num_arcs None: four arcs a state) that is the plan.  Otherwise a quarter of the
+    budget is set aside for nodes and arcs, one node to four arcs, and the rest is planned as for
+    the 1-best search.  node_cap never needs to exceed log_cap."""
+    tables = 12 * num_states + 8 * (T + 2)
+    if workspace_bytes < tables + 20 + 24 + 16 + 16 + 64:
+        raise ValueError("workspace_bytes = %d cannot hold one utterance's tables (%d bytes)"
+                         % (workspace_bytes, tables + 140))
+    rec = (T + 1) * num_states
+    arcs = max(1, (T + 1) * (4 * num_states if num_arcs is None else num_arcs))
+    full = tables + 20 * num_states + (24 + 16) * rec + 16 * arcs + 64
+    if 4 * (workspace_bytes // full) >= B and max(rec, arcs) < 2 ** 31 - 1:
+        return int(min(B, workspace_bytes // full)), int(num_states), int(rec), int(rec), int(arcs)
+    search = workspace_bytes - workspace_bytes // 4
+    chunk = B if B * tables <= search // 2 else max(1, (search // 2) // tables)
+    chunk = max(1, min(chunk, B, workspace_bytes // (tables + 20 + 24 + 32 + 64)))
+    rest = search // chunk - tables - 64
+    list_cap = int(min(num_states, max(1, rest // 4 // 20), 2 ** 31 - 2))
+    log_cap = int(min((T + 1) * list_cap, max(1, (rest - 20 * list_cap) // 24), 2 ** 31 - 2))
+    out = (workspace_bytes // 4) // chunk
+    node_cap = int(min(log_cap, max(1, out // 5 // 16)))
+    arc_cap = int(min(2 ** 31 - 2, max(1, (out - 16 * node_cap) // 16)))
+    return chunk, list_cap, log_cap, node_cap, arc_cap
+
+
+THREADS_PER_WORKGROUP = 0       # 0: the kernel's default; 256 / 512 / 1024 for timing runs
+
+
+def _decode_device(lp, lens, graph, beam, lattice_beam, scale, allow_partial, workspace_bytes, pack=True):
+    """launches asr_wfst_lattice_f32; returns per-utterance counts and the kept nodes and arcs of the
+    whole batch, packed utterance after utterance and already in canonical order, as numpy arrays:
+    only those cross to the host.  pack=False (tools/bench_wfst_lattice.py): the launches alone."""
+    T, B, C = lp.shape
+    L = _native.lib()
+    g = graph
+    if not L.asr_wfst_lattice_supported(g.num_states, len(g.src), C, T):
+        raise NotImplementedError(
+            "asr_wfst_lattice_f32 serves 1 <= C <= 4096 classes and T >= 1 (got C = %d, T = %d); "
+            "ASR_WFST_LATTICE_NATIVE=0 selects the host path" % (C, T))
+    dev = lp.device
+    d = g.device_arrays(dev)
+    lens_d = torch.as_tensor(np.asarray(lens, np.int32)).to(dev)
+    chunk, list_cap, log_cap, node_cap, arc_cap = plan_workspace(g.num_states, T, B, workspace_bytes, len(g.src))
+    nbytes = L.asr_wfst_lattice_workspace_bytes(g.num_states, chunk, T, list_cap, log_cap)
+    if not 0 < nbytes:
+        raise ValueError("workspace_bytes = %d is too small" % workspace_bytes)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    cost = torch.empty(B, **f32)
+    final, overflow, n_nodes, n_arcs = (torch.empty(B, **i32) for _ in range(4))
+    p = _native._p
+    packed = [[] for _ in range(8)]
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        nb = b1 - b0
+        node_i = torch.empty((2, nb, node_cap), **i32)      # time, state
+        node_f = torch.empty((2, nb, node_cap), **f32)      # alpha, beta
+        arc_i = torch.empty((3, nb, arc_cap), **i32)        # src, dst, arc
+        arc_f = torch.empty((nb, arc_cap), **f32)           # lp
+        _native.check(L.asr_wfst_lattice_f32(
+            p(lp[:, b0]), B * C, p(lens_d[b0:]), T, nb, C, g.num_states, len(g.src),
+            p(d['ptr']), p(d['src']), p(d['dst']), p(d['il']), p(d['ol']), p(d['w']), p(d['fin']),
+            p(d['eps_ptr']), p(d['eps_arc']), len(g.eps_arc), p(d['rank']), g.num_ranks, g.start,
+            float(beam), float(lattice_beam), float(scale), int(bool(allow_partial)),
+            list_cap, log_cap, node_cap, arc_cap, int(THREADS_PER_WORKGROUP),
+            p(cost[b0:]), p(final[b0:]), p(n_nodes[b0:]), p(n_arcs[b0:]),
+            p(node_i[0]), p(node_i[1]), p(node_f[0]), p(node_f[1]),
+            p(arc_i[0]), p(arc_i[1]), p(arc_i[2]), p(arc_f), p(overflow[b0:]),
+            p(ws), nbytes, _native._stream()), 'asr_wfst_lattice_f32')
+        if not pack:
+            continue
+        ok = overflow[b0:b1] == 0
+        rows = torch.arange(nb, device=dev)
+
+        def used(count, cap):
+            """flat indices of the first count[b] slots of every row of a [nb, cap] array, and the rows"""
+            count = torch.where(ok, count, torch.zeros_like(count)).long()
+            total = int(count.sum())                # the one read-back the packing needs
+            r = torch.repeat_interleave(rows, count, output_size=total)
+            first = torch.cumsum(count, 0) - count
+            return r * cap + (torch.arange(total, device=dev) - first[r]), r, first
+        ni, n_utt, n_first = used(n_nodes[b0:b1], node_cap)
+        ai, a_utt, _ = used(n_arcs[b0:b1], arc_cap)
+        time, state = node_i[0].reshape(-1)[ni].long(), node_i[1].reshape(-1)[ni].long()
+        # canonical order, here where sorting is cheap: nodes by (utterance, time, state) ...
+        order = _order((n_utt, time, state), (nb, T + 1, g.num_states))
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(len(order), device=dev)
+        # ... arcs by (utterance, src node, graph arc index); src / dst renumbered within the utterance
+        src = rank[arc_i[0].reshape(-1)[ai].long() + n_first[a_utt]]
+        dst = rank[arc_i[1].reshape(-1)[ai].long() + n_first[a_utt]]
+        arc = arc_i[2].reshape(-1)[ai].long() & 0xFFFFFFFF
+        ao = _order((src, arc), (max(1, len(order)), max(1, len(g.src))))        # src is global: utterance-major
+        for j, t in enumerate((time[order].int(), state[order].int(), node_f[0].reshape(-1)[ni][order],
+                               node_f[1].reshape(-1)[ni][order], (src - n_first[a_utt])[ao].int(),
+                               (dst - n_first[a_utt])[ao].int(), arc[ao], arc_f.reshape(-1)[ai][ao])):
+            packed[j].append(t)
+    if not pack:
+        return None
+    packed = [torch.cat(x).cpu().numpy() for x in packed]
+    return (cost.cpu().numpy(), final.cpu().numpy(), n_nodes.cpu().numpy(), n_arcs.cpu().numpy(),
+            overflow.cpu().numpy(), packed)
+
+
+def _order(keys, bounds):
+    """argsort of rows by `keys` (int64 tensors, most significant first, 0 <= key < bound): one sort
+    of a composite key when it fits 62 bits, else stable sorts from the least significant key up"""
+    span = 1
+    for b in bounds:
+        span *= int(b)
+    if span < 2 ** 62:
+        key = keys[0]
+        for k, b in zip(keys[1:], bounds[1:]):
+            key = key * int(b) + k
+        return torch.sort(key)[1]
+    order = torch.sort(keys[-1], stable=True)[1]
+    for k in reversed(keys[:-1]):
+        order = order[torch.sort(k[order], stable=True)[1]]
+    return order
+
+
+def _validate(log_probs, lens, graph, beam, lattice_beam):
+    if not isinstance(log_probs, torch.Tensor):
+        log_probs = torch.as_tensor(np.asarray(log_probs, np.float32))
+    if log_probs.dim() != 3:
+        raise ValueError("log_probs must be [T, B, C]")
+    T, B, C = log_probs.shape
+    if graph.max_ilabel > C:
+        raise ValueError("the graph reads class %d but log_probs has C = %d classes"
+                         % (graph.max_ilabel - 1, C))
+    if not (float(beam) >= 0.0):
+        raise ValueError("beam must be >= 0")
+    if not (float(lattice_beam) >= 0.0):
+        raise ValueError("lattice_beam must be >= 0")
+    lens_np = np.asarray(torch.as_tensor(lens).cpu(), np.int64).reshape(-1)
+    if len(lens_np) != B:
+        raise ValueError("lens must have one entry per utterance")
+    if len(lens_np) and (lens_np.min() < 1 or lens_np.max() > T):
+        raise ValueError("lens must lie in [1, T]")
+    lp = log_probs.detach()
+    if lp.dtype != torch.float32:
+        lp = lp.float()
+    return lp, lens_np
+
+
+def decode_lattice(log_probs, lens, graph, beam=16.0, lattice_beam=8.0, acoustic_scale=1.0,
+                   allow_partial=True, workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+    """One search per utterance, one `Lattice` per utterance: (lattices, redone_on_host).
+
+    Arguments as decode_graph, plus lattice_beam >= 0 (+inf: every arc the search saw that lies on
+    a complete path).  A GPU tensor runs asr_wfst_lattice_f32; a CPU tensor, or
+    ASR_WFST_LATTICE_NATIVE=0 (read per call), the host path, which gives the same bits.  An
+    utterance that outgrows the device's token lists, its log, or the node or arc capacity
+    (plan_workspace) is redone on the host, with one warning per call."""
+    lp, lens_np = _validate(log_probs, lens, graph, beam, lattice_beam)
+    T, B, C = lp.shape
+    native = lp.is_cuda and os.environ.get('ASR_WFST_LATTICE_NATIVE', '1') != '0'
+    if not native or B == 0 or T == 0:
+        lats, _ = decode_lattice_host(lp.cpu().numpy(), lens_np, graph, beam, lattice_beam, acoustic_scale,
+                                      allow_partial)
+        return lats, []
+    lp = lp.contiguous()
+    cost, final, n_nodes, n_arcs, overflow, packed = _decode_device(
+        lp, lens_np, graph, beam, lattice_beam, acoustic_scale, allow_partial, int(workspace_bytes))
+    redo = np.nonzero(overflow)[0].tolist()
+    n_nodes = np.where(overflow != 0, 0, n_nodes)
+    n_arcs = np.where(overflow != 0, 0, n_arcs)
+    no = np.r_[0, np.cumsum(n_nodes)]
+    ao = np.r_[0, np.cumsum(n_arcs)]
+    lats = []
+    for b in range(B):
+        ns, as_ = slice(no[b], no[b + 1]), slice(ao[b], ao[b + 1])
+        if overflow[b] or n_nodes[b] == 0:
+            lats.append(_empty(graph, acoustic_scale, lens_np[b]))
+            continue
+        lats.append(Lattice(graph, acoustic_scale, lens_np[b], cost[b], final[b] != 0,
+                            *[x[ns] for x in packed[:4]], *[x[as_] for x in packed[4:]]))
+    if redo:
+        warnings.warn("decode_lattice: %d of %d utterances outgrew the device workspace (%s; "
+                      "workspace_bytes = %d) and were decoded on the host"
+                      % (len(redo), B, ', '.join(sorted({OVERFLOW_NAMES.get(int(overflow[b]), '?') for b in redo})),
+                         workspace_bytes))
+        idx = torch.as_tensor(redo, device=lp.device)
+        h, _ = decode_lattice_host(lp[:, idx].cpu().numpy(), lens_np[redo], graph, beam, lattice_beam,
+                                   acoustic_scale, allow_partial)
+        for j, b in enumerate(redo):
+            lats[b] = h[j]
+    return lats, redo

@@ -4,12 +4,19 @@ reference's scoring recipe (egs/wsj/ctc_kaldi_decode.sh:141-147) without Kaldi.
 
     python tools/decode_graph.py LOGPROBS.ark GRAPH.fst [--words words.txt] [--beam 16]
         [--acoustic-scale 1.0] [--batch 64] [--device cuda:0|cpu] [--out FILE]
+        [--lattice-beam X --nbest N [--acwt-sweep LO:HI:STEP]]
 
 LOGPROBS.ark: the float-matrix archive att_speech.ctc_forward writes (one [frames, classes] matrix
 per utterance).  GRAPH.fst: an OpenFst binary (vector/standard, plain or gzip) or an AT&T text
 file whose input label i > 0 reads class i - 1.  One line `uttid w1 w2 ...` per utterance, in
 archive order: the integer transcript decode-faster writes to `ark,t:`, or symbols with --words
-(what int2sym.pl makes of it).  An utterance without a path is written with no words."""
+(what int2sym.pl makes of it).  An utterance without a path is written with no words.
+
+With --lattice-beam the search keeps a lattice (att_speech.wfst_lattice.decode_lattice:
+latgen-faster) and the output is its n-best list, `uttid-k cost w1 w2 ...` for k = 1..N, cheapest
+first.  With --acwt-sweep as well, the one search (at --acoustic-scale) is re-ranked on the host
+for every scale LO, LO + STEP, ..., HI, which the recipe does with one decode-faster run per scale
+(egs/wsj/ctc_kaldi_decode.sh:160-163): lines `scale uttid cost w1 w2 ...`, scale by scale."""
 import argparse
 import os
 import sys
@@ -23,6 +30,70 @@ import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
 
+def parse_sweep(text):
+    """'LO:HI:STEP' -> the scales LO, LO + STEP, ... up to HI (inclusive, to 1e-9)"""
+    lo, hi, step = (float(x) for x in text.split(':'))
+    if not (step > 0 and hi >= lo):
+        raise ValueError("--acwt-sweep wants LO:HI:STEP with STEP > 0 and HI >= LO")
+    return [round(lo + i * step, 9) for i in range(int((hi - lo) / step + 1e-9) + 1)]
+
+
+def _batches(utts, batch):
+    """utts: [(key, [frames, classes] matrix)] -> (keys, lp [T,B,C] zero-padded, lens) per batch"""
+    for i in range(0, len(utts), max(1, batch)):
+        part = utts[i:i + max(1, batch)]
+        lens = np.array([m.shape[0] for _, m in part], np.int32)
+        if lens.min() < 1:
+            raise ValueError("empty matrix in the archive")
+        lp = np.zeros((int(lens.max()), len(part), part[0][1].shape[1]), np.float32)
+        for j, (_, m) in enumerate(part):
+            lp[:lens[j], j] = m
+        yield [k for k, _ in part], lp, lens
+
+
+def _lattices(graph, utts, device, batch, **kw):
+    from att_speech import wfst_lattice
+    for keys, lp, lens in _batches(utts, batch):
+        lats, _ = wfst_lattice.decode_lattice(torch.from_numpy(lp).to(device), lens, graph, **kw)
+        for k, lat in zip(keys, lats):
+            yield k, lat
+
+
+def _tokens(table, words):
+    return [table.find(int(w)) or str(w) for w in words] if table else [str(w) for w in words]
+
+
+def write_nbest(graph, utts, path, beam, lattice_beam, nbest, acoustic_scale=1.0, allow_partial=True,
+                device='cpu', batch=64, table=None):
+    """`uttid-k cost w1 w2 ...`: the nbest cheapest distinct word sequences of every utterance"""
+    out = open(path, 'w') if path else sys.stdout
+    try:
+        for key, lat in _lattices(graph, utts, device, batch, beam=beam, lattice_beam=lattice_beam,
+                                  acoustic_scale=acoustic_scale, allow_partial=allow_partial):
+            for k, (words, cost) in enumerate(lat.nbest(nbest)):
+                out.write(' '.join(['%s-%d' % (key, k + 1), '%.6f' % cost] + _tokens(table, words)) + '\n')
+    finally:
+        if path:
+            out.close()
+
+
+def write_sweep(graph, utts, path, beam, lattice_beam, scales, acoustic_scale=1.0, allow_partial=True,
+                device='cpu', batch=64, table=None):
+    """`scale uttid cost w1 w2 ...`: the best path of every utterance at every scale, from one search"""
+    lats = list(_lattices(graph, utts, device, batch, beam=beam, lattice_beam=lattice_beam,
+                          acoustic_scale=acoustic_scale, allow_partial=allow_partial))
+    out = open(path, 'w') if path else sys.stdout
+    try:
+        from att_speech.wfst_lattice import LatticeBatch
+        every = LatticeBatch([lat for _, lat in lats])
+        for scale in scales:
+            for (key, _), (words, cost, _, _) in zip(lats, every.best_paths(acoustic_scale=scale)):
+                out.write(' '.join(['%g' % scale, key, '%.6f' % cost] + _tokens(table, words)) + '\n')
+    finally:
+        if path:
+            out.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('logprobs')
@@ -34,7 +105,12 @@ def main(argv=None):
     ap.add_argument('--device', default=None, help='default: cuda:0 when there is one, else cpu')
     ap.add_argument('--no-allow-partial', action='store_true')
     ap.add_argument('--out', default=None, help='default: standard output')
+    ap.add_argument('--lattice-beam', type=float, default=None, help='keep a lattice this wide; write its n-best')
+    ap.add_argument('--nbest', type=int, default=1)
+    ap.add_argument('--acwt-sweep', default=None, help='LO:HI:STEP: the 1-best per acoustic scale from one search')
     a = ap.parse_args(argv)
+    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1):
+        ap.error('--nbest and --acwt-sweep need --lattice-beam')
     from att_speech import wfst_decode
     from att_speech.ctc_forward import read_kaldi_float_matrices
     from att_speech.lm_fst import SymbolTable
@@ -43,6 +119,15 @@ def main(argv=None):
     table = SymbolTable.read_text(a.words) if a.words else None
     mats = read_kaldi_float_matrices(a.logprobs)
     keys = list(mats)
+    if a.lattice_beam is not None:
+        utts = [(k, mats[k]) for k in keys]
+        kw = dict(beam=a.beam, lattice_beam=a.lattice_beam, acoustic_scale=a.acoustic_scale,
+                  allow_partial=not a.no_allow_partial, device=device, batch=a.batch, table=table)
+        if a.acwt_sweep:
+            write_sweep(graph, utts, a.out, scales=parse_sweep(a.acwt_sweep), **kw)
+        else:
+            write_nbest(graph, utts, a.out, nbest=a.nbest, **kw)
+        return
     out = open(a.out, 'w') if a.out else sys.stdout
     try:
         for i in range(0, len(keys), max(1, a.batch)):
