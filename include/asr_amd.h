@@ -1246,6 +1246,79 @@ int asr_wfst_lattice_f32(const float *lp, int64_t frame_stride, const int32_t *l
                          int32_t *out_overflow, void *workspace, int64_t workspace_bytes,
                          void *stream);
 
+/*
+ * Dynamic programmes over a batch of such lattices that stays on the device (csrc/lattice_dp.hip,
+ * DESIGN.md section 4.21): re-ranking under any number of (acoustic scale, LM scale) pairs in one
+ * launch (lattice-best-path per scale), and arc / node posteriors by a log-semiring
+ * forward-backward (lattice-to-post).  Additions again: the ABI version stays 24.
+ *
+ * The batch: B lattices laid end to end, N nodes, A arcs, in the canonical form (nodes by
+ * (utterance, time, state), arcs by (utterance, source node, graph arc index)).
+ *   node_off, arc_off, level_off [B+1] i64, on the device, and h_* the same words on the host: from
+ *     0 to N / A / L, never decreasing (checked on the host copies before anything is launched)
+ *   node_time, node_state [N] i32; node_level [N] i32 the node's level, an index into level_ptr:
+ *     levels ascend by (utterance, time, epsilon rank of the state) and every arc rises in level
+ *   lat_src, lat_dst [A] i32 node indices within the utterance, lat_arc [A] i64 arc index in the
+ *     graph, lat_lp [A] f32 the unscaled class score (0 on non-emitting arcs)
+ *   level_ptr [L+1] i32, level_node [N] i32: the nodes (batch indices) of level l are
+ *     level_node[level_ptr[l] .. level_ptr[l+1]); utterance b owns the levels level_off[b] ..
+ *   in_ptr [N+1] i32, in_arc [A] i32: the in-arcs (batch indices) of node v, in the stored order
+ *   out_ptr [N+1] i32: the out-arcs of node v are the arcs out_ptr[v] .. out_ptr[v+1]
+ *   num_frames, reached_final [B] i32; own_scale [B] f64 the acoustic scale of each search
+ *   the graph: arc_weight [G] f32, arc_olabel [G] i32, final_cost [num_states] f32, start
+ *   b_begin, b_count: the utterances this launch serves (the workspace covers their nodes only)
+ *   threads: 0 (= 64), 64, 128 or 256 lanes per workgroup
+ *
+ * Arc cost x = fl(fl(lm w) - fl(sc lp)) in fp64, no contraction; end(v) = final(state) at time
+ * num_frames when reached_final, 0 at that time otherwise, +inf elsewhere.
+ *
+ * asr_lattice_bestpath_f64: per pair p (acoustic_scales[p] NaN: own_scale) and utterance
+ *   cost(start) = 0, cost(v) = min over in-arcs of cost(u) + x; back-pointer: of the in-arcs that
+ *   attain it and are finite, the smallest graph arc index; winner: the smallest node index among the
+ *   minima of cost(v) + fl(lm end(v)); traceback from there, graph cost = end + sum of w, acoustic
+ *   cost = - sum of lp, added in that order.  IEEE semantics as numpy: a NaN among the utterance's
+ *   costs means no path.  No path: (+inf, +inf, +inf) and 0 words.
+ *   out_cost [P,B,3] f64 (cost, graph cost, acoustic cost), out_num_words [P,B] i32, out_words [P,L]
+ *   i32 (utterance b's words of pair p start at p L + level_off[b]; a path has at most one arc per
+ *   level), out_status [P,B] i32: 1 when an index read from the arrays was out of range or a level
+ *   did not rise (the utterance then has no result).
+ *   workspace: asr_lattice_bestpath_workspace_bytes(nodes of the launch, P) = 12 bytes per node and
+ *   pair, rounded.  One workgroup per (pair, utterance), workgroup barriers only.
+ *
+ * asr_lattice_posterior_f64: fwd(start) = 0, fwd(v) = logsumexp over in-arcs of fwd(u) - x; bwd(v) =
+ *   logsumexp of -fl(lm end(v)) (end nodes) and bwd(d) - x over out-arcs; each by one lane in the
+ *   stored order, max then sum: no atomics on results, run-to-run identical bits.
+ *   out_log_z [B] = bwd(start) (-inf: no lattice), out_arc_log_post [A] = fwd(src) - x + bwd(dst) -
+ *   log_z, out_node_log_post [N] = fwd + bwd - log_z (-inf where a term is), out_status [B] as above.
+ *   workspace: asr_lattice_posterior_workspace_bytes(nodes of the launch) = 16 bytes per node, rounded.
+ */
+int asr_lattice_bestpath_supported(int64_t N, int64_t A, int64_t L);
+int64_t asr_lattice_bestpath_workspace_bytes(int64_t num_nodes, int num_pairs);
+int asr_lattice_bestpath_f64(
+    int B, int b_begin, int b_count, int num_pairs, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
+    const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
+    const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
+    const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
+    const double *acoustic_scales, const double *lm_scales, int64_t num_states, int64_t num_graph_arcs,
+    const float *arc_weight, const int32_t *arc_olabel, const float *final_cost, int start, int threads,
+    double *out_cost, int32_t *out_num_words, int32_t *out_words, int32_t *out_status, void *workspace,
+    int64_t workspace_bytes, void *stream);
+int asr_lattice_posterior_supported(int64_t N, int64_t A, int64_t L);
+int64_t asr_lattice_posterior_workspace_bytes(int64_t num_nodes);
+int asr_lattice_posterior_f64(
+    int B, int b_begin, int b_count, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
+    const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
+    const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
+    const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
+    double acoustic_scale, double lm_scale, int64_t num_states, int64_t num_graph_arcs, const float *arc_weight,
+    const int32_t *arc_olabel, const float *final_cost, int start, int threads, double *out_log_z,
+    double *out_arc_log_post, double *out_node_log_post, int32_t *out_status, void *workspace,
+    int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,14 @@ _SIGNATURES = {
     'asr_wfst_lattice_workspace_bytes': (_i64, [_i64, _i, _i, _i64, _i64]),
     'asr_wfst_lattice_f32': (_i, [_vp, _i64, _vp, _i, _i, _i, _i64, _i64] + [_vp] * 9 + [_i64, _vp, _i, _i,
                                   _f, _f, _f, _i, _i64, _i64, _i64, _i64, _i] + [_vp] * 14 + [_i64, _vp]),
+    'asr_lattice_bestpath_supported': (_i, [_i64, _i64, _i64]),
+    'asr_lattice_bestpath_workspace_bytes': (_i64, [_i64, _i]),
+    'asr_lattice_bestpath_f64': (_i, [_i, _i, _i, _i, _i64, _i64, _i64] + [_vp] * 23 + [_i64, _i64] + [_vp] * 3 +
+                                 [_i, _i] + [_vp] * 5 + [_i64, _vp]),
+    'asr_lattice_posterior_supported': (_i, [_i64, _i64, _i64]),
+    'asr_lattice_posterior_workspace_bytes': (_i64, [_i64]),
+    'asr_lattice_posterior_f64': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
+                                  [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 5 + [_i64, _vp]),
     'asr_split_bf16_f32': (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     'asr_log_softmax_shift_bwd_split_blocks': (_i, [_i64]),
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),

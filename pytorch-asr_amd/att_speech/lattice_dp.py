@@ -1,0 +1,387 @@
+"""Lattices that stay on the device, and the two dynamic programmes run over them there.
+
+`decode_lattice_device` is att_speech.wfst_lattice.decode_lattice without the copy to the host: the
+same launch, the same canonical sort on the device, and a `DeviceLatticeBatch` instead of a list of
+`Lattice`.  The batch re-ranks itself under any number of (acoustic scale, LM scale) pairs in one
+launch (`best_paths`: the recipe's acoustic-scale sweep, egs/wsj/ctc_kaldi_decode.sh:160-163, as one
+search plus one sweep) and computes arc, node, frame and word posteriors (`posteriors`:
+lattice-to-post).  DESIGN.md section 4.21.
+
+A batch on a GPU runs asr_lattice_bestpath_f64 / asr_lattice_posterior_f64 (csrc/lattice_dp.hip); a
+batch of CPU tensors, or ASR_LATTICE_DP_NATIVE=0 (read per call), the host path: LatticeBatch of
+att_speech.wfst_lattice, which gives the same bits for best paths and the same posteriors within
+rounding.
+"""
+import ctypes
+import os
+import warnings
+
+import numpy as np
+import torch
+
+from att_speech import _native
+from att_speech.wfst_decode import DEFAULT_WORKSPACE_BYTES
+from att_speech.wfst_lattice import (INF, OVERFLOW_NAMES, Lattice, LatticeBatch, LatticePosteriors, _decode_device,
+                                     _order, _validate, decode_lattice_host)
+
+THREADS_PER_WORKGROUP = 0       # 0: the kernels' default (64); 128 / 256 for timing runs
+
+
+def _h(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _scale_list(v):
+    if v is None or isinstance(v, (int, float, np.floating, np.integer)):
+        return [v], True
+    return list(v), False
+
+
+class DeviceLatticeBatch(object):
+    """The lattices of B utterances over one DecodingGraph as tensors on one device, in the canonical
+    form of wfst_lattice.Lattice, utterance after utterance:
+
+      time, state [N] int32, alpha, beta [N] float32        nodes by (utterance, time, state)
+      src, dst [A] int32 (node indices within the utterance), arc [A] int64, lp [A] float32
+                                                             arcs by (utterance, src, graph arc)
+      node_off, arc_off [B+1] int64 (numpy, and *_d on the device), num_frames [B], reached_final [B],
+      cost [B] float32, acoustic_scale [B] float64 (numpy: per utterance, the scale of its search)
+
+    and the level structure the dynamic programmes walk, built once with torch ops on the device: a
+    node's level is (time, graph.rank[state]) and every arc rises in level;
+
+      node_level [N], level_ptr [L+1], level_node [N], level_off [B+1]   the nodes level by level
+      in_ptr [N+1], in_arc [A]                                           the in-arcs of every node
+      out_ptr [N+1]                                                      its out-arcs: a range of arcs
+
+    Malformed arrays (an end point outside the utterance, a level that does not rise, arcs not sorted
+    by source) raise ValueError here, before any kernel sees them."""
+
+    def __init__(self, graph, device, time, state, alpha, beta, src, dst, arc, lp, node_count, arc_count,
+                 num_frames, reached_final, cost, acoustic_scale, max_frames=None, num_classes=None,
+                 workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+        self.graph, self.device = graph, torch.device(device)
+        dev = self.device
+        self.time, self.state = time.to(dev, torch.int32), state.to(dev, torch.int32)
+        self.alpha, self.beta = alpha.to(dev, torch.float32), beta.to(dev, torch.float32)
+        self.src, self.dst = src.to(dev, torch.int32), dst.to(dev, torch.int32)
+        self.arc, self.lp = arc.to(dev, torch.int64), lp.to(dev, torch.float32)
+        node_count = np.asarray(node_count, np.int64).reshape(-1)
+        arc_count = np.asarray(arc_count, np.int64).reshape(-1)
+        B = self.num_utterances = len(node_count)
+        self.num_frames = np.asarray(num_frames, np.int32).reshape(-1)
+        self.reached_final = np.asarray(reached_final, bool).reshape(-1)
+        self.cost = np.asarray(cost, np.float32).reshape(-1)
+        self.acoustic_scale = np.asarray(acoustic_scale, np.float64).reshape(-1)
+        if not (len(arc_count) == len(self.num_frames) == len(self.reached_final) == len(self.cost)
+                == len(self.acoustic_scale) == B):
+            raise ValueError("per-utterance arrays disagree in length")
+        if (node_count < 0).any() or (arc_count < 0).any():
+            raise ValueError("offsets must not decrease")
+        self.node_off = np.r_[0, np.cumsum(node_count)].astype(np.int64)
+        self.arc_off = np.r_[0, np.cumsum(arc_count)].astype(np.int64)
+        N, A = self.num_nodes, self.num_arcs = int(self.node_off[-1]), int(self.arc_off[-1])
+        if not (len(self.time) == len(self.state) == len(self.alpha) == len(self.beta) == N):
+            raise ValueError("node arrays disagree with the node counts")
+        if not (len(self.src) == len(self.dst) == len(self.arc) == len(self.lp) == A):
+            raise ValueError("arc arrays disagree with the arc counts")
+        if max(N, A) >= 2 ** 31 - 1:
+            raise NotImplementedError("a batch holds fewer than 2^31 - 1 nodes and arcs")
+        self.max_frames = int(self.num_frames.max()) if max_frames is None and B else int(max_frames or 0)
+        self.num_classes = graph.max_ilabel if num_classes is None else int(num_classes)
+        self.workspace_bytes = int(workspace_bytes)
+        self._host = None
+        self._build_levels()
+
+    # ---- the level structure ------------------------------------------------------------
+    def _build_levels(self):
+        g, dev, B, N, A = self.graph, self.device, self.num_utterances, self.num_nodes, self.num_arcs
+        i64 = dict(dtype=torch.int64, device=dev)
+        self.node_off_d = torch.from_numpy(self.node_off).to(dev)
+        self.arc_off_d = torch.from_numpy(self.arc_off).to(dev)
+        counts = self.node_off_d[1:] - self.node_off_d[:-1]
+        self.node_utt = torch.repeat_interleave(torch.arange(B, **i64), counts, output_size=N)
+        self.arc_utt = torch.repeat_interleave(torch.arange(B, **i64), self.arc_off_d[1:] - self.arc_off_d[:-1],
+                                               output_size=A)
+        time, state = self.time.long(), self.state.long()
+        src, dst = self.src.long(), self.dst.long()
+        n_of = counts[self.arc_utt]
+        bad = 0
+        if N:
+            bad = bad + ((state < 0) | (state >= g.num_states) | (time < 0)).sum()
+        if A:
+            bad = bad + ((src < 0) | (src >= n_of) | (dst < 0) | (dst >= n_of)).sum()
+            bad = bad + ((self.arc < 0) | (self.arc >= len(g.src))).sum()
+        if (N or A) and int(bad):               # one read-back for all the range checks
+            raise ValueError("lattice arrays out of range: a node's state or time, an arc's end point "
+                             "outside its utterance, or an arc index outside the graph")
+        self.src_global = src + self.node_off_d[self.arc_utt]
+        self.dst_global = dst + self.node_off_d[self.arc_utt]
+        R = g.num_ranks + 1
+        rank = g.device_arrays(dev)['rank'].long()
+        t_max = int(time.max()) + 1 if N else 1
+        key = time * R + rank[state] if N else time
+        perm = _order((self.node_utt, key, state), (max(1, B), t_max * R, g.num_states)) if N else time
+        ck = (self.node_utt * (t_max * R) + key)[perm]
+        new = torch.ones(N, dtype=torch.bool, device=dev)
+        if N > 1:
+            new[1:] = ck[1:] != ck[:-1]
+        level_sorted = torch.cumsum(new.long(), 0) - 1
+        first = torch.nonzero(new).reshape(-1)
+        L = self.num_levels = int(first.numel())
+        node_level = torch.empty(N, **i64)
+        node_level[perm] = level_sorted
+        self.level_ptr = torch.cat([first, torch.full((1,), N, **i64)]).int()
+        self.level_node = perm.int()
+        self.node_level = node_level.int()
+        level_utt = self.node_utt[perm][first]
+        self.level_off_d = torch.searchsorted(level_utt, torch.arange(B + 1, **i64))
+        self.level_off = self.level_off_d.cpu().numpy().astype(np.int64)
+        if A:
+            rises = node_level[self.src_global] < node_level[self.dst_global]
+            ordered = self.src_global[1:] >= self.src_global[:-1] if A > 1 else rises
+            if not bool(rises.all() & ordered.all()):
+                raise ValueError("every lattice arc must lead to a higher (time, epsilon rank) level, and the "
+                                 "arcs must be sorted by source node")
+        ends = torch.arange(N + 1, **i64)
+        order = torch.sort(self.dst_global, stable=True)[1] if A else self.dst_global
+        self.in_arc = order.int()
+        self.in_ptr = torch.searchsorted(self.dst_global[order].contiguous(), ends).int()
+        self.out_ptr = torch.searchsorted(self.src_global.contiguous(), ends).int()
+        self.frames_d = torch.from_numpy(self.num_frames).to(dev)
+        self.reached_d = torch.from_numpy(self.reached_final.astype(np.int32)).to(dev)
+        self.scale_d = torch.from_numpy(self.acoustic_scale).to(dev)
+
+    @property
+    def ilabel(self):
+        """[A] the input label of every arc (0: epsilon), on the device"""
+        return self.graph.device_arrays(self.device)['il'][self.arc]
+
+    # ---- construction ---------------------------------------------------------------------
+    @classmethod
+    def from_lattices(cls, lattices, device, graph=None, **kw):
+        """Upload host `Lattice` objects over one graph (empty ones included: utterances without a
+        lattice keep their place)."""
+        lats = list(lattices)
+        if graph is None:
+            if not lats:
+                raise ValueError("from_lattices needs a lattice or the graph")
+            graph = lats[0].graph
+
+        def cat(name, dtype):
+            parts = [np.asarray(getattr(l, name), dtype) for l in lats]
+            return torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, dtype))
+        return cls(graph, device, cat('time', np.int32), cat('state', np.int32), cat('alpha', np.float32),
+                   cat('beta', np.float32), cat('src', np.int32), cat('dst', np.int32), cat('arc', np.int64),
+                   cat('lp', np.float32), [l.num_nodes for l in lats], [l.num_arcs for l in lats],
+                   [l.num_frames for l in lats], [l.reached_final for l in lats], [l.cost for l in lats],
+                   [l.acoustic_scale for l in lats], **kw)
+
+    def lattices(self):
+        """The batch as host `Lattice` objects, field for field what decode_lattice returns."""
+        host = [getattr(self, k).cpu().numpy() for k in Lattice.FIELDS]
+        out = []
+        for b in range(self.num_utterances):
+            ns = slice(self.node_off[b], self.node_off[b + 1])
+            as_ = slice(self.arc_off[b], self.arc_off[b + 1])
+            out.append(Lattice(self.graph, self.acoustic_scale[b], self.num_frames[b], self.cost[b],
+                               self.reached_final[b], *[x[ns] for x in host[:4]], *[x[as_] for x in host[4:]]))
+        return out
+
+    def _host_batch(self):
+        if self._host is None:
+            self._host = LatticeBatch(self.lattices())
+        return self._host
+
+    def _on_device(self):
+        return self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_DP_NATIVE', '1') != '0'
+
+    def _common_args(self):
+        p = _native._p
+        g = self.graph.device_arrays(self.device)
+        head = (self.num_nodes, self.num_arcs, self.num_levels, _h(self.node_off), _h(self.arc_off),
+                _h(self.level_off), p(self.node_off_d), p(self.arc_off_d), p(self.level_off_d), p(self.time),
+                p(self.state), p(self.node_level), p(self.src), p(self.dst), p(self.arc), p(self.lp),
+                p(self.level_ptr), p(self.level_node), p(self.in_ptr), p(self.in_arc), p(self.out_ptr),
+                p(self.frames_d), p(self.reached_d), p(self.scale_d))
+        tail = (self.graph.num_states, len(self.graph.src), p(g['w']), p(g['ol']), p(g['fin']), self.graph.start,
+                int(THREADS_PER_WORKGROUP))
+        return head, tail
+
+    def _utterance_chunks(self, bytes_per_node, budget):
+        """[b0, b1) ranges whose nodes fit the budget"""
+        out, b0 = [], 0
+        B = self.num_utterances
+        while b0 < B:
+            b1 = b0 + 1
+            while b1 < B and (self.node_off[b1 + 1] - self.node_off[b0]) * bytes_per_node + 64 <= budget:
+                b1 += 1
+            if (self.node_off[b1] - self.node_off[b0]) * bytes_per_node + 64 > budget:
+                raise ValueError("workspace_bytes = %d cannot hold utterance %d's %d nodes (%d bytes a node)"
+                                 % (budget, b0, self.node_off[b1] - self.node_off[b0], bytes_per_node))
+            out.append((b0, b1))
+            b0 = b1
+        return out
+
+    @staticmethod
+    def _check(code, what):
+        if code == _native.ASR_EINVAL:
+            raise ValueError("%s: %s" % (what, _native.lib().asr_strerror(code).decode()))
+        _native.check(code, what)
+
+    # ---- the tropical sweep -----------------------------------------------------------------
+    def best_paths(self, acoustic_scales=None, lm_scales=1.0, workspace_bytes=None):
+        """The best path of every lattice under every (acoustic scale, LM scale) pair.
+
+        acoustic_scales: a float, None (each lattice's own search scale) or a sequence of those;
+        lm_scales: a float or a sequence of the same length.  Returns one list per pair (a single
+        float or None is one pair), each what LatticeBatch(lattices).best_paths(sc, lm) returns:
+        (words, cost, graph_cost, acoustic_cost) per utterance, bit for bit.  On a GPU all pairs
+        and utterances are one launch of asr_lattice_bestpath_f64, or several when workspace_bytes
+        (default: the batch's) does not hold 12 bytes per node and pair at once."""
+        acs, _ = _scale_list(acoustic_scales)
+        lms, one = _scale_list(lm_scales)
+        if one:
+            lms = lms * len(acs)
+        if len(lms) != len(acs):
+            raise ValueError("lm_scales must be a float or as long as acoustic_scales")
+        P, B = len(acs), self.num_utterances
+        if not self._on_device():
+            hb = self._host_batch()
+            with np.errstate(invalid='ignore'):
+                return [hb.best_paths(sc, lm) for sc, lm in zip(acs, lms)]
+        none = ([], INF, INF, INF)
+        if P == 0 or B == 0 or self.num_nodes == 0:
+            return [[none] * B for _ in range(P)]
+        L = _native.lib()
+        if not L.asr_lattice_bestpath_supported(self.num_nodes, self.num_arcs, self.num_levels):
+            raise NotImplementedError("asr_lattice_bestpath_f64: the batch is too large")
+        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
+        dev, p = self.device, _native._p
+        per_launch = max(1, min(P, (budget - 64) // max(1, 12 * self.num_nodes)))
+        chunks = self._utterance_chunks(12 * per_launch, budget)
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        ac_d = torch.tensor([float('nan') if a is None else float(a) for a in acs], **f64)
+        lm_d = torch.tensor([float(x) for x in lms], **f64)
+        cost = torch.empty((P, B, 3), **f64)
+        n_words = torch.zeros((P, B), **i32)
+        words = torch.zeros((P, max(1, self.num_levels)), **i32)
+        status = torch.zeros((P, B), **i32)
+        head, tail = self._common_args()
+        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
+        nbytes = L.asr_lattice_bestpath_workspace_bytes(biggest, per_launch)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.launches = 0
+        for p0 in range(0, P, per_launch):
+            np_ = min(per_launch, P - p0)
+            for b0, b1 in chunks:
+                self._check(L.asr_lattice_bestpath_f64(
+                    B, b0, b1 - b0, np_, *head, p(ac_d[p0:]), p(lm_d[p0:]), *tail,
+                    p(cost[p0:]), p(n_words[p0:]), p(words[p0:]), p(status[p0:]), p(ws), nbytes,
+                    _native._stream()), 'asr_lattice_bestpath_f64')
+                self.launches += 1
+        cost_h, nw_h, words_h = cost.cpu().numpy(), n_words.cpu().numpy(), words.cpu().numpy()
+        if status.cpu().numpy().any():
+            raise ValueError("asr_lattice_bestpath_f64: the batch's index arrays are inconsistent")
+        out = []
+        for k in range(P):
+            row = []
+            for b in range(B):
+                c = cost_h[k, b]
+                if not c[0] < INF:
+                    row.append(none)
+                    continue
+                o = int(self.level_off[b])
+                row.append((words_h[k, o:o + nw_h[k, b]].tolist(), float(c[0]), float(c[1]), float(c[2])))
+            out.append(row)
+        return out
+
+    # ---- the log-semiring pass ----------------------------------------------------------------
+    def posteriors(self, acoustic_scale=None, lm_scale=1.0, workspace_bytes=None):
+        """Arc and node posteriors under the path weights exp(-(sum of x + lm_scale * end)), x and end
+        as in best_paths: a LatticePosteriors (log_z [B], arc_log_post [A], node_log_post [N] in
+        fp64, frame_posteriors(), word_posteriors()).  On a GPU one launch of
+        asr_lattice_posterior_f64 does forward and backward (several when workspace_bytes does not
+        hold 16 bytes per node at once); two runs give the same bits."""
+        if not self._on_device():
+            post = self._host_batch().posteriors(acoustic_scale, lm_scale)
+            if self.device.type == 'cuda':
+                post = LatticePosteriors(self, *[torch.from_numpy(np.asarray(x, np.float64)).to(self.device) for x in
+                                                 (post.log_z, post.arc_log_post, post.node_log_post)],
+                                         acoustic_scale, lm_scale)
+            return post
+        B, dev, p = self.num_utterances, self.device, _native._p
+        f64 = dict(dtype=torch.float64, device=dev)
+        log_z = torch.full((B,), -INF, **f64)
+        arc_post = torch.full((self.num_arcs,), -INF, **f64)
+        node_post = torch.full((self.num_nodes,), -INF, **f64)
+        res = LatticePosteriors(self, log_z, arc_post, node_post, acoustic_scale, lm_scale)
+        if B == 0 or self.num_nodes == 0:
+            return res
+        L = _native.lib()
+        if not L.asr_lattice_posterior_supported(self.num_nodes, self.num_arcs, self.num_levels):
+            raise NotImplementedError("asr_lattice_posterior_f64: the batch is too large")
+        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
+        chunks = self._utterance_chunks(16, budget)
+        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
+        nbytes = L.asr_lattice_posterior_workspace_bytes(biggest)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        head, tail = self._common_args()
+        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
+        for b0, b1 in chunks:
+            self._check(L.asr_lattice_posterior_f64(
+                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(log_z), p(arc_post), p(node_post),
+                p(status), p(ws), nbytes, _native._stream()), 'asr_lattice_posterior_f64')
+        if status.cpu().numpy().any():
+            raise ValueError("asr_lattice_posterior_f64: the batch's index arrays are inconsistent")
+        return res
+
+
+def decode_lattice_device(log_probs, lens, graph, beam=16.0, lattice_beam=8.0, acoustic_scale=1.0,
+                          allow_partial=True, workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+    """decode_lattice whose lattices stay where the search left them: (DeviceLatticeBatch,
+    redone_on_host).  The same launch and the same canonical sort on the device; nothing but the
+    per-utterance counts crosses to the host.  batch.lattices() is decode_lattice's list.  An
+    utterance that outgrows the device workspace is decoded by decode_lattice_host as there (one
+    warning per call) and its lattice is uploaded into its place.  CPU tensors, or
+    ASR_WFST_LATTICE_NATIVE=0: the host search, uploaded to the tensor's device."""
+    lp, lens_np = _validate(log_probs, lens, graph, beam, lattice_beam)
+    T, B, C = lp.shape
+    kw = dict(graph=graph, max_frames=T, num_classes=C, workspace_bytes=workspace_bytes)
+    native = lp.is_cuda and os.environ.get('ASR_WFST_LATTICE_NATIVE', '1') != '0'
+    if not native or B == 0 or T == 0:
+        lats, _ = decode_lattice_host(lp.cpu().numpy(), lens_np, graph, beam, lattice_beam, acoustic_scale,
+                                      allow_partial)
+        return DeviceLatticeBatch.from_lattices(lats, lp.device, **kw), []
+    lp = lp.contiguous()
+    cost, final, n_nodes, n_arcs, overflow, packed = _decode_device(
+        lp, lens_np, graph, beam, lattice_beam, acoustic_scale, allow_partial, int(workspace_bytes), to_host=False)
+    cost, final, n_nodes, n_arcs, overflow = (x.cpu().numpy() for x in (cost, final, n_nodes, n_arcs, overflow))
+    redo = np.nonzero(overflow)[0].tolist()
+    n_nodes = np.where(overflow != 0, 0, n_nodes).astype(np.int64)
+    n_arcs = np.where(overflow != 0, 0, n_arcs).astype(np.int64)
+    gone = n_nodes == 0
+    cost = np.where(gone, np.float32(INF), cost)
+    reached = np.where(gone, False, final != 0)
+    n_arcs = np.where(gone, 0, n_arcs)
+    if redo:
+        warnings.warn("decode_lattice: %d of %d utterances outgrew the device workspace (%s; "
+                      "workspace_bytes = %d) and were decoded on the host"
+                      % (len(redo), B, ', '.join(sorted({OVERFLOW_NAMES.get(int(overflow[b]), '?') for b in redo})),
+                         workspace_bytes))
+        idx = torch.as_tensor(redo, device=lp.device)
+        h, _ = decode_lattice_host(lp[:, idx].cpu().numpy(), lens_np[redo], graph, beam, lattice_beam,
+                                   acoustic_scale, allow_partial)
+        pieces = [list(torch.split(x, (n_nodes if j < 4 else n_arcs).tolist())) for j, x in enumerate(packed)]
+        for lat, b in zip(h, redo):
+            for j, name in enumerate(Lattice.FIELDS):
+                pieces[j][b] = torch.from_numpy(np.asarray(getattr(lat, name))).to(lp.device).to(packed[j].dtype)
+            n_nodes[b], n_arcs[b] = lat.num_nodes, lat.num_arcs
+            cost[b], reached[b] = lat.cost, lat.reached_final
+        packed = [torch.cat(x) for x in pieces]
+    kw.pop('graph')
+    batch = DeviceLatticeBatch(graph, lp.device, *packed, n_nodes, n_arcs, lens_np, reached, cost,
+                               np.full(B, float(acoustic_scale)), **kw)
+    return batch, redo

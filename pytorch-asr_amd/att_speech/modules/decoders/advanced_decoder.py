@@ -603,16 +603,21 @@ class FSTDecoder(_ProjectionDecoder):
                  graph_generator, normalize_by_dim=None,
                  numerator_red='logsumexp', denominator_red='logsumexp',
                  embedder='LutLinear', embedder_kwargs={}, decode_beam=None,
-                 decode_lattice_beam=None, decode_nbest=1, **kwargs):
+                 decode_lattice_beam=None, decode_nbest=1, decode_confidence=False, **kwargs):
         super(FSTDecoder, self).__init__(**kwargs)
         # decode_beam: None = the exact every-state Viterbi below; a number = the beam-pruned
         # token-passing search (att_speech/wfst_decode.py) over the same graph with that beam
         # decode_lattice_beam: None = the 1-best search alone; a number = one lattice search
         # (att_speech/wfst_lattice.py) with that lattice beam, and decode() adds 'nbest': per
         # utterance the decode_nbest cheapest distinct label sequences as (labels, cost)
+        # decode_confidence: decode() also adds 'word_confidence': per utterance one posterior for
+        # each label of the lattice's best path at the search scale (att_speech/lattice_dp.py:
+        # posteriors().word_posteriors(window=0)); the lattice then stays on the device
         if decode_lattice_beam is not None and decode_beam is None:
             raise ValueError("decode_lattice_beam needs decode_beam: the lattice comes from the beam search")
-        self.decode_beam = decode_beam
+        if decode_confidence and decode_lattice_beam is None:
+            raise ValueError("decode_confidence needs decode_lattice_beam: the posteriors are the lattice's")
+        self.decode_beam, self.decode_confidence = decode_beam, bool(decode_confidence)
         self.decode_lattice_beam, self.decode_nbest = decode_lattice_beam, int(decode_nbest)
         self._decoding_graph = None
         gg = utils.contruct_from_kwargs(
@@ -721,7 +726,15 @@ class FSTDecoder(_ProjectionDecoder):
             res = wfst_decode.decode_graph(logits.detach().float(), encoded_lens, self._decoding_graph,
                                            beam=float(self.decode_beam))
             ret = {'decoded': res['words'], 'logits': logits}   # the labels on the winning arcs
-            if self.decode_lattice_beam is not None:
+            if self.decode_lattice_beam is not None and self.decode_confidence:
+                from att_speech import lattice_dp
+                batch, _ = lattice_dp.decode_lattice_device(
+                    logits.detach().float(), encoded_lens, self._decoding_graph, beam=float(self.decode_beam),
+                    lattice_beam=float(self.decode_lattice_beam))
+                ret['nbest'] = [lat.nbest(self.decode_nbest) for lat in batch.lattices()]
+                ret['word_confidence'] = [[p for _, _, p in row]
+                                          for row in batch.posteriors().word_posteriors(window=0)]
+            elif self.decode_lattice_beam is not None:
                 from att_speech import wfst_lattice
                 lats, _ = wfst_lattice.decode_lattice(
                     logits.detach().float(), encoded_lens, self._decoding_graph, beam=float(self.decode_beam),

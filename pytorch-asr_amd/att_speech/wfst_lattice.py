@@ -107,6 +107,10 @@ class Lattice(object):
         end state, as in the search.  No lattice: ([], inf, inf, inf)."""
         return LatticeBatch([self]).best_paths(acoustic_scale, lm_scale)[0]
 
+    def posteriors(self, acoustic_scale=None, lm_scale=1.0):
+        """LatticeBatch.posteriors of this lattice alone"""
+        return LatticeBatch([self]).posteriors(acoustic_scale, lm_scale)
+
     def nbest(self, n, acoustic_scale=None, lm_scale=1.0, max_expansions=DEFAULT_MAX_EXPANSIONS):
         """The n cheapest DISTINCT word sequences as [(words, cost)], sorted by (cost, words).
 
@@ -217,12 +221,16 @@ class LatticeBatch(object):
 
     def best_paths(self, acoustic_scale=None, lm_scale=1.0):
         """Lattice.best_path for every lattice: a list of (words, cost, graph_cost, acoustic_cost)"""
+        return self._best_paths(acoustic_scale, lm_scale)[0]
+
+    def _best_paths(self, acoustic_scale=None, lm_scale=1.0):
+        """(best_paths' list, per utterance the batch arc indices of the path's word-bearing arcs)"""
         none = ([], INF, INF, INF)
         if not self.lattices:
-            return []
+            return [], []
         B, N = len(self.lattices), len(self.time)
         if not N:
-            return [none] * B
+            return [none] * B, [[] for _ in range(B)]
         sc = self.scale if acoustic_scale is None else float(acoustic_scale)
         x = float(lm_scale) * self.w - sc * self.lp
         cost = np.where(self.start, 0.0, INF)
@@ -249,7 +257,7 @@ class LatticeBatch(object):
         gc[live] = np.where(self.end[v[live]] < INF, self.end[v[live]], 0.0)
         ac = np.zeros(B)
         cur = np.where(live, v, 0)
-        w_utt, w_lab, w_step = [], [], []
+        w_utt, w_lab, w_step, w_arc = [], [], [], []
         for step in range(len(self.levels) + 1):       # a path has at most one arc per level
             j = np.where(live, bp[cur], -1)
             live = j >= 0
@@ -262,15 +270,133 @@ class LatticeBatch(object):
             has = self.ol[ju] != 0
             w_utt.append(u[has])
             w_lab.append(self.ol[ju][has])
+            w_arc.append(ju[has])
             w_step.append(np.full(int(has.sum()), step))
             cur[u] = self.src[ju]
         words = [[] for _ in range(B)]
+        arcs = [[] for _ in range(B)]
         if w_utt:
             wu, wl, ws = np.concatenate(w_utt), np.concatenate(w_lab), np.concatenate(w_step)
+            wa = np.concatenate(w_arc)
             for i in np.lexsort((-ws, wu)):             # per utterance, the last step first: path order
                 words[wu[i]].append(int(wl[i]))
-        return [(words[b], float(best[b]), float(gc[b]), float(ac[b])) if best[b] < INF else none
-                for b in range(B)]
+                arcs[wu[i]].append(int(wa[i]))
+        return ([(words[b], float(best[b]), float(gc[b]), float(ac[b])) if best[b] < INF else none
+                 for b in range(B)], [arcs[b] if best[b] < INF else [] for b in range(B)])
+
+    def posteriors(self, acoustic_scale=None, lm_scale=1.0):
+        """Arc and node posteriors of every lattice under the path weights exp(-(sum of x + lm_scale *
+        end)), x = lm_scale * w - acoustic_scale * lp as in best_paths: one log-semiring
+        forward-backward in fp64 over the levels.  Returns a LatticePosteriors.  A final cost of +inf
+        ends no path, whatever lm_scale is."""
+        B = len(self.lattices)
+        N = len(self.time) if B else 0
+        if not N:
+            return LatticePosteriors(self, np.full(B, -INF), np.zeros(0), np.zeros(0), acoustic_scale, lm_scale)
+        sc = self.scale if acoustic_scale is None else float(acoustic_scale)
+        lm = float(lm_scale)
+        x = lm * self.w - sc * self.lp
+        fwd = np.where(self.start, 0.0, -INF)
+        with np.errstate(invalid='ignore'):
+            stop = np.where(self.end < INF, -(lm * np.where(self.end < INF, self.end, 0.0)), -INF)
+            bwd = stop.copy()
+            for lv, src, _, _ in self.levels:
+                ok = fwd[src] > -INF
+                np.logaddexp.at(fwd, self.dst[lv][ok], fwd[src][ok] - x[lv][ok])
+            for lv, src, _, _ in reversed(self.levels):
+                d = self.dst[lv]
+                ok = bwd[d] > -INF
+                np.logaddexp.at(bwd, src[ok], bwd[d][ok] - x[lv][ok])
+            first = np.full(B, N, np.int64)
+            np.minimum.at(first, self.n_utt[self.start], np.nonzero(self.start)[0])
+            log_z = np.where(first < N, bwd[np.minimum(first, N - 1)], -INF)
+            zn = log_z[self.n_utt]
+            node = np.where((fwd > -INF) & (bwd > -INF) & (zn > -INF), fwd + bwd - zn, -INF)
+            a_utt = self.n_utt[self.src]
+            za = log_z[a_utt]
+            part = fwd[self.src] - x
+            arc = np.where((fwd[self.src] > -INF) & (bwd[self.dst] > -INF) & (za > -INF),
+                           part + bwd[self.dst] - za, -INF)
+        return LatticePosteriors(self, log_z, arc, node, acoustic_scale, lm_scale)
+
+
+class LatticePosteriors(object):
+    """What LatticeBatch.posteriors and DeviceLatticeBatch.posteriors return.
+
+    log_z [B], arc_log_post [total arcs], node_log_post [total nodes]: fp64, numpy arrays from the
+    host path and tensors on the batch's device from the device path; arcs and nodes in the batch's
+    order, utterance after utterance.  log_z is -inf for an utterance without a lattice."""
+
+    def __init__(self, batch, log_z, arc_log_post, node_log_post, acoustic_scale, lm_scale):
+        self.batch, self.log_z, self.arc_log_post, self.node_log_post = batch, log_z, arc_log_post, node_log_post
+        self.acoustic_scale, self.lm_scale = acoustic_scale, lm_scale
+
+    def _host_batch(self):
+        b = self.batch
+        return b if isinstance(b, LatticeBatch) else LatticeBatch(b.lattices())
+
+    def frame_posteriors(self, num_frames=None, num_classes=None):
+        """[T, B, C] float32: entry (k - 1, b, c) is the posterior mass of the emitting arcs of
+        utterance b into time k that read class c (ilabel c + 1): the recipe toolchain's
+        lattice-to-post.  Zero beyond the utterance's frames.  T defaults to the longest utterance
+        (the device batch remembers its log_probs' T), C to the largest class the graph reads."""
+        b = self.batch
+        if isinstance(b, LatticeBatch):
+            lats = b.lattices
+            B = len(lats)
+            T = max([l.num_frames for l in lats] + [0]) if num_frames is None else int(num_frames)
+            C = (b.graph.max_ilabel if B else 0) if num_classes is None else int(num_classes)
+            out = torch.zeros((T, B, C), dtype=torch.float32)
+            if not B or not len(b.arc):
+                return out
+            il = torch.from_numpy(b.graph.ilabel[b.arc])
+            k = torch.from_numpy(b.time[b.dst])
+            utt = torch.from_numpy(b.n_utt[b.src])
+            post = torch.from_numpy(np.asarray(self.arc_log_post))
+        else:
+            B = b.num_utterances
+            T = b.max_frames if num_frames is None else int(num_frames)
+            C = b.num_classes if num_classes is None else int(num_classes)
+            out = torch.zeros((T, B, C), dtype=torch.float32, device=b.device)
+            if not B or not b.num_arcs:
+                return out
+            il = b.ilabel.long()
+            k = b.time.long()[b.dst_global]
+            utt = b.arc_utt
+            post = self.arc_log_post
+        em = il > 0
+        if bool(((il[em] > C) | (k[em] > T)).any()):
+            raise ValueError("frame_posteriors: the lattice has classes or frames beyond [T, B, C] = %s"
+                             % (tuple(out.shape),))
+        flat = ((k[em] - 1) * B + utt[em]) * C + (il[em] - 1)
+        acc = torch.zeros(T * B * C, dtype=torch.float64, device=out.device)
+        acc.index_add_(0, flat, torch.exp(post[em]))
+        return acc.reshape(T, B, C).float()
+
+    def word_posteriors(self, window=0):
+        """Per utterance a list of (word, frame, posterior), one entry for each word-bearing arc of
+        the best path at these scales: the summed posterior of the utterance's arcs that carry the
+        same word and end within `window` frames of that arc's end time, clipped to 1.  Computed
+        on the host.  This is a time-window confidence (how much of the lattice's probability mass
+        agrees that the word is spoken there), not Kaldi's MBR confidence: no edit-distance
+        alignment between paths is made."""
+        hb = self._host_batch()
+        _, word_arcs = hb._best_paths(self.acoustic_scale, self.lm_scale)
+        post = self.arc_log_post
+        post = np.exp(post.cpu().numpy() if isinstance(post, torch.Tensor) else np.asarray(post))
+        out = []
+        if not hb.lattices or not len(hb.time):
+            return [[] for _ in hb.lattices]
+        t_end = hb.time[hb.dst]
+        a_utt = hb.n_utt[hb.src]
+        for b, arcs in enumerate(word_arcs):
+            mine = np.nonzero(a_utt == b)[0]
+            row = []
+            for j in arcs:
+                same = mine[(hb.ol[mine] == hb.ol[j]) & (np.abs(t_end[mine] - t_end[j]) <= int(window))]
+                row.append((int(hb.ol[j]), int(t_end[j]), float(min(1.0, post[same].sum()))))
+            out.append(row)
+        return out
 
 
 def best_paths(lattices, acoustic_scale=None, lm_scale=1.0):
@@ -478,10 +604,13 @@ def plan_workspace(num_states, T, B, workspace_bytes, num_arcs=None):
 THREADS_PER_WORKGROUP = 0       # 0: the kernel's default; 256 / 512 / 1024 for timing runs
 
 
-def _decode_device(lp, lens, graph, beam, lattice_beam, scale, allow_partial, workspace_bytes, pack=True):
+def _decode_device(lp, lens, graph, beam, lattice_beam, scale, allow_partial, workspace_bytes, pack=True,
+                   to_host=True):
     """launches asr_wfst_lattice_f32; returns per-utterance counts and the kept nodes and arcs of the
     whole batch, packed utterance after utterance and already in canonical order, as numpy arrays:
-    only those cross to the host.  pack=False (tools/bench_wfst_lattice.py): the launches alone."""
+    only those cross to the host.  pack=False (tools/bench_wfst_lattice.py): the launches alone.
+    to_host=False (att_speech.lattice_dp.decode_lattice_device): the same as device tensors, nothing
+    is copied."""
     T, B, C = lp.shape
     L = _native.lib()
     g = graph
@@ -550,9 +679,11 @@ def _decode_device(lp, lens, graph, beam, lattice_beam, scale, allow_partial, wo
             packed[j].append(t)
     if not pack:
         return None
-    packed = [torch.cat(x).cpu().numpy() for x in packed]
+    packed = [torch.cat(x) for x in packed]
+    if not to_host:
+        return cost, final, n_nodes, n_arcs, overflow, packed
     return (cost.cpu().numpy(), final.cpu().numpy(), n_nodes.cpu().numpy(), n_arcs.cpu().numpy(),
-            overflow.cpu().numpy(), packed)
+            overflow.cpu().numpy(), [x.cpu().numpy() for x in packed])
 
 
 def _order(keys, bounds):

@@ -4,7 +4,7 @@ reference's scoring recipe (egs/wsj/ctc_kaldi_decode.sh:141-147) without Kaldi.
 
     python tools/decode_graph.py LOGPROBS.ark GRAPH.fst [--words words.txt] [--beam 16]
         [--acoustic-scale 1.0] [--batch 64] [--device cuda:0|cpu] [--out FILE]
-        [--lattice-beam X --nbest N [--acwt-sweep LO:HI:STEP]]
+        [--lattice-beam X --nbest N [--acwt-sweep LO:HI:STEP] [--post OUT.npz]]
 
 LOGPROBS.ark: the float-matrix archive att_speech.ctc_forward writes (one [frames, classes] matrix
 per utterance).  GRAPH.fst: an OpenFst binary (vector/standard, plain or gzip) or an AT&T text
@@ -14,9 +14,12 @@ archive order: the integer transcript decode-faster writes to `ark,t:`, or symbo
 
 With --lattice-beam the search keeps a lattice (att_speech.wfst_lattice.decode_lattice:
 latgen-faster) and the output is its n-best list, `uttid-k cost w1 w2 ...` for k = 1..N, cheapest
-first.  With --acwt-sweep as well, the one search (at --acoustic-scale) is re-ranked on the host
-for every scale LO, LO + STEP, ..., HI, which the recipe does with one decode-faster run per scale
-(egs/wsj/ctc_kaldi_decode.sh:160-163): lines `scale uttid cost w1 w2 ...`, scale by scale."""
+first.  With --acwt-sweep as well, the one search (at --acoustic-scale) is re-ranked for every scale
+LO, LO + STEP, ..., HI, which the recipe does with one decode-faster run per scale
+(egs/wsj/ctc_kaldi_decode.sh:160-163): lines `scale uttid cost w1 w2 ...`, scale by scale.  The
+lattices stay on the device and all scales are one call (att_speech.lattice_dp).  With --post the
+frame-level class posteriors of every lattice (lattice-to-post) go to OUT.npz, one
+[frames, classes] float32 matrix per utterance key, and nothing else is written."""
 import argparse
 import os
 import sys
@@ -80,18 +83,37 @@ def write_nbest(graph, utts, path, beam, lattice_beam, nbest, acoustic_scale=1.0
 def write_sweep(graph, utts, path, beam, lattice_beam, scales, acoustic_scale=1.0, allow_partial=True,
                 device='cpu', batch=64, table=None):
     """`scale uttid cost w1 w2 ...`: the best path of every utterance at every scale, from one search"""
-    lats = list(_lattices(graph, utts, device, batch, beam=beam, lattice_beam=lattice_beam,
-                          acoustic_scale=acoustic_scale, allow_partial=allow_partial))
+    from att_speech.lattice_dp import decode_lattice_device
+    rows = [[] for _ in scales]
+    for keys, lp, lens in _batches(utts, batch):
+        every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, beam=beam,
+                                         lattice_beam=lattice_beam, acoustic_scale=acoustic_scale,
+                                         allow_partial=allow_partial)
+        for row, best in zip(rows, every.best_paths(scales)):
+            row.extend(zip(keys, best))
     out = open(path, 'w') if path else sys.stdout
     try:
-        from att_speech.wfst_lattice import LatticeBatch
-        every = LatticeBatch([lat for _, lat in lats])
-        for scale in scales:
-            for (key, _), (words, cost, _, _) in zip(lats, every.best_paths(acoustic_scale=scale)):
+        for scale, row in zip(scales, rows):
+            for key, (words, cost, _, _) in row:
                 out.write(' '.join(['%g' % scale, key, '%.6f' % cost] + _tokens(table, words)) + '\n')
     finally:
         if path:
             out.close()
+
+
+def write_post(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_partial=True, device='cpu',
+               batch=64, table=None):
+    """OUT.npz: per utterance key the [frames, classes] posteriors of its lattice at the search's scales"""
+    from att_speech.lattice_dp import decode_lattice_device
+    mats = {}
+    for keys, lp, lens in _batches(utts, batch):
+        every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, beam=beam,
+                                         lattice_beam=lattice_beam, acoustic_scale=acoustic_scale,
+                                         allow_partial=allow_partial)
+        post = every.posteriors().frame_posteriors().cpu().numpy()
+        for j, key in enumerate(keys):
+            mats[key] = post[:lens[j], j]
+    np.savez(path, **mats)
 
 
 def main(argv=None):
@@ -108,9 +130,10 @@ def main(argv=None):
     ap.add_argument('--lattice-beam', type=float, default=None, help='keep a lattice this wide; write its n-best')
     ap.add_argument('--nbest', type=int, default=1)
     ap.add_argument('--acwt-sweep', default=None, help='LO:HI:STEP: the 1-best per acoustic scale from one search')
+    ap.add_argument('--post', default=None, help='OUT.npz: frame-level class posteriors of every lattice')
     a = ap.parse_args(argv)
-    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1):
-        ap.error('--nbest and --acwt-sweep need --lattice-beam')
+    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post):
+        ap.error('--nbest, --acwt-sweep and --post need --lattice-beam')
     from att_speech import wfst_decode
     from att_speech.ctc_forward import read_kaldi_float_matrices
     from att_speech.lm_fst import SymbolTable
@@ -123,7 +146,9 @@ def main(argv=None):
         utts = [(k, mats[k]) for k in keys]
         kw = dict(beam=a.beam, lattice_beam=a.lattice_beam, acoustic_scale=a.acoustic_scale,
                   allow_partial=not a.no_allow_partial, device=device, batch=a.batch, table=table)
-        if a.acwt_sweep:
+        if a.post:
+            write_post(graph, utts, a.post, **kw)
+        elif a.acwt_sweep:
             write_sweep(graph, utts, a.out, scales=parse_sweep(a.acwt_sweep), **kw)
         else:
             write_nbest(graph, utts, a.out, nbest=a.nbest, **kw)
