@@ -1319,6 +1319,54 @@ int asr_lattice_posterior_f64(
     double *out_arc_log_post, double *out_node_log_post, int32_t *out_status, void *workspace,
     int64_t workspace_bytes, void *stream);
 
+/*
+ * asr_lattice_nbest_f64: the n cheapest DISTINCT word sequences of every lattice of such a batch, in
+ * one launch (csrc/lattice_dp.hip; LatticeBatch.nbest of
+ * att_speech/wfst_lattice.py is its numpy twin and gives the same bits).  Additions: the ABI version
+ * stays 24.  The batch, b_begin / b_count and x as above; threads: 64, 128 or 256 lanes per workgroup,
+ * 0 = 256 (a wave per node: four nodes of a level at a time); acoustic_scale NaN: own_scale.
+ *
+ * A k-best dynamic programme backwards over the levels.  Every node v keeps a list of at most n
+ * entries (c, len, h, arc, rank): the cost of a word suffix from v to an end, its number of words, a
+ * 64-bit hash of it, the out-arc taken (-1: stop at v), the index into the list of that arc's
+ * destination.  e(v) = fl(lm final(state)) at time num_frames when reached_final, 0 at that time
+ * otherwise, +inf elsewhere.  The candidates of v:
+ *   the stop entry (e(v), 0, 0, -1, 0) when e(v) < +inf;
+ *   for every out-arc j and every entry r of list(dst_j): c' = fl(x_j + c_r), dropped unless
+ *   c' < +inf (which drops NaN too), len' = len_r + (olabel_j != 0), h' = olabel_j != 0 ?
+ *   h_r * 0x9E3779B97F4A7C15 + olabel_j + 1 (mod 2^64) : h_r.
+ * They are ordered by (c', len', h', arc, rank) ascending; of candidates with equal (len', h') only
+ * the first survives; list(v) is the first n survivors.  Two suffixes are the same sequence iff
+ * (len, h) agree: a 64-bit hash identity, and a collision would drop one of two sequences from a
+ * list, nothing else.  The result is this order's, whatever the schedule: no atomics on results.
+ * Read-out: the entries of the start node (time 0, state `start`) are followed forwards along (arc,
+ * rank); the non-zero output labels are the words, and the cost is summed forwards, g = 0,
+ * g = fl(g + x_j) per arc, then fl(g + e(end)), as LatticeBatch.best_paths sums it.
+ *   out_count [B] i32 entries of utterance b (0: no nodes, no start node or no finite path);
+ *   out_cost [B, n] f64, out_num_words [B, n] i32, in the list's order (the caller sorts by (cost,
+ *   words)); out_words [n L] i32: the words of entry i of utterance b start at n level_off[b] +
+ *   i levels(b) (a path has at most one arc per level); out_status [B] i32 as above, also raised by
+ *   a rank outside the destination's list or an entry whose destination does not sit higher.
+ *   n: 1 .. ASR_LATTICE_NBEST_MAX (more: ASR_EUNSUPPORTED; less: ASR_EINVAL).
+ *   workspace: asr_lattice_nbest_workspace_bytes(nodes of the launch, n) = n entries of 28 bytes (cost
+ *   f64, hash u64, len, arc, rank i32) and one i32 count per node, rounded.  The outputs are not part
+ *   of it.  One workgroup per utterance, one wave per node of a level, workgroup barriers only.
+ */
+#define ASR_LATTICE_NBEST_MAX 64
+int asr_lattice_nbest_supported(int64_t N, int64_t A, int64_t L, int n);
+int64_t asr_lattice_nbest_workspace_bytes(int64_t num_nodes, int n);
+int asr_lattice_nbest_f64(
+    int B, int b_begin, int b_count, int n, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
+    const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
+    const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
+    const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
+    double acoustic_scale, double lm_scale, int64_t num_states, int64_t num_graph_arcs, const float *arc_weight,
+    const int32_t *arc_olabel, const float *final_cost, int start, int threads, int32_t *out_count,
+    double *out_cost, int32_t *out_num_words, int32_t *out_words, int32_t *out_status, void *workspace,
+    int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

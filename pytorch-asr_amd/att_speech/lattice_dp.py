@@ -5,12 +5,13 @@ same launch, the same canonical sort on the device, and a `DeviceLatticeBatch` i
 `Lattice`.  The batch re-ranks itself under any number of (acoustic scale, LM scale) pairs in one
 launch (`best_paths`: the recipe's acoustic-scale sweep, egs/wsj/ctc_kaldi_decode.sh:160-163, as one
 search plus one sweep) and computes arc, node, frame and word posteriors (`posteriors`:
-lattice-to-post).  DESIGN.md section 4.21.
+lattice-to-post).  DESIGN.md section 4.21.  `nbest` / `sentences` list its n cheapest distinct word
+sequences, the hand-over to AttentionDecoderTCN.score_sentences, in one launch (section 4.22).
 
-A batch on a GPU runs asr_lattice_bestpath_f64 / asr_lattice_posterior_f64 (csrc/lattice_dp.hip); a
-batch of CPU tensors, or ASR_LATTICE_DP_NATIVE=0 (read per call), the host path: LatticeBatch of
-att_speech.wfst_lattice, which gives the same bits for best paths and the same posteriors within
-rounding.
+A batch on a GPU runs asr_lattice_bestpath_f64 / asr_lattice_posterior_f64 / asr_lattice_nbest_f64
+(csrc/lattice_dp.hip); a batch of CPU tensors, or ASR_LATTICE_DP_NATIVE=0 (ASR_LATTICE_NBEST_NATIVE=0
+for nbest; both read per call), the host path: LatticeBatch of att_speech.wfst_lattice, which gives
+the same bits for best paths and n-best lists and the same posteriors within rounding.
 """
 import ctypes
 import os
@@ -22,9 +23,10 @@ import torch
 from att_speech import _native
 from att_speech.wfst_decode import DEFAULT_WORKSPACE_BYTES
 from att_speech.wfst_lattice import (INF, OVERFLOW_NAMES, Lattice, LatticeBatch, LatticePosteriors, _decode_device,
-                                     _order, _validate, decode_lattice_host)
+                                     _order, _validate, decode_lattice_host, nbest_lists)
 
-THREADS_PER_WORKGROUP = 0       # 0: the kernels' default (64); 128 / 256 for timing runs
+THREADS_PER_WORKGROUP = 0       # 0: the kernels' default (64; nbest: 256); 64 / 128 / 256 for timing runs
+NBEST_DEVICE_MAX = 64           # ASR_LATTICE_NBEST_MAX of include/asr_amd.h: a list entry per lane of a wave
 
 
 def _h(a):
@@ -296,6 +298,74 @@ class DeviceLatticeBatch(object):
                 row.append((words_h[k, o:o + nw_h[k, b]].tolist(), float(c[0]), float(c[1]), float(c[2])))
             out.append(row)
         return out
+
+    # ---- n-best lists --------------------------------------------------------------------------
+    def nbest(self, n, acoustic_scale=None, lm_scale=1.0, workspace_bytes=None):
+        """The n cheapest DISTINCT word sequences of every lattice: one [(words, cost)] per utterance,
+        sorted by (cost, words); the semantics are LatticeBatch.nbest's (a
+        k-best dynamic programme over the levels, sequences told apart by a 64-bit hash of their
+        words, ties at the n-th cost cut by (length, hash) where Lattice.nbest cuts by the words).
+
+        On a GPU all utterances are one launch of asr_lattice_nbest_f64, or several when
+        workspace_bytes (default: the batch's) does not hold 28 n + 4 bytes per node at once.  A
+        batch of CPU tensors, ASR_LATTICE_NBEST_NATIVE=0 (read per call) and n above
+        NBEST_DEVICE_MAX run LatticeBatch.nbest on a copy: the same bits in every case."""
+        n = int(n)
+        B = self.num_utterances
+        native = (self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_NBEST_NATIVE', '1') != '0'
+                  and n <= NBEST_DEVICE_MAX)
+        if not native:
+            return self._host_batch().nbest(n, acoustic_scale, lm_scale)
+        if n < 1 or B == 0 or self.num_nodes == 0:
+            return [[] for _ in range(B)]
+        count, status, cost, n_words, words = self._nbest_launch(n, acoustic_scale, lm_scale, workspace_bytes)
+        packed = torch.cat([count, status, n_words.reshape(-1)]).cpu().numpy()     # the small ones in one read-back
+        count_h, status_h, nw_h = packed[:B], packed[B:2 * B], packed[2 * B:].reshape(B, n)
+        if status_h.any():
+            raise ValueError("asr_lattice_nbest_f64: the batch's index arrays are inconsistent")
+        cost_h, words_h = cost.cpu().numpy(), words.cpu().numpy()
+        levels = np.diff(self.level_off)
+        utt, rows, costs = [], [], []
+        for b in np.nonzero(count_h)[0].tolist():
+            base, lv = n * int(self.level_off[b]), int(levels[b])
+            for i in range(int(count_h[b])):
+                o = base + i * lv
+                utt.append(b)
+                rows.append(words_h[o:o + nw_h[b, i]].tolist())
+                costs.append(float(cost_h[b, i]))
+        return nbest_lists(B, utt, rows, costs)
+
+    def _nbest_launch(self, n, acoustic_scale, lm_scale, workspace_bytes):
+        """the launches of nbest alone: (count [B], status [B], cost [B, n], n_words [B, n], words [n L]) on
+        the device, as asr_lattice_nbest_f64 leaves them"""
+        B = self.num_utterances
+        L = _native.lib()
+        if not L.asr_lattice_nbest_supported(self.num_nodes, self.num_arcs, self.num_levels, n):
+            raise NotImplementedError("asr_lattice_nbest_f64: the batch is too large")
+        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
+        dev, p = self.device, _native._p
+        chunks = self._utterance_chunks(28 * n + 4, budget - 128)       # 128: the rounding of the six arrays
+        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
+        nbytes = L.asr_lattice_nbest_workspace_bytes(biggest, n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        count, status = torch.zeros(B, **i32), torch.zeros(B, **i32)
+        cost = torch.empty((B, n), dtype=torch.float64, device=dev)
+        n_words = torch.zeros((B, n), **i32)
+        words = torch.zeros(n * max(1, self.num_levels), **i32)
+        head, tail = self._common_args()
+        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
+        self.launches = 0
+        for b0, b1 in chunks:
+            self._check(L.asr_lattice_nbest_f64(
+                B, b0, b1 - b0, n, *head, sc, float(lm_scale), *tail, p(count), p(cost), p(n_words), p(words),
+                p(status), p(ws), nbytes, _native._stream()), 'asr_lattice_nbest_f64')
+            self.launches += 1
+        return count, status, cost, n_words, words
+
+    def sentences(self, n, **kw):
+        """the word lists of nbest(n) per utterance: what AttentionDecoderTCN.score_sentences takes"""
+        return [[w for w, _ in row] for row in self.nbest(n, **kw)]
 
     # ---- the log-semiring pass ----------------------------------------------------------------
     def posteriors(self, acoustic_scale=None, lm_scale=1.0, workspace_bytes=None):

@@ -603,7 +603,8 @@ class FSTDecoder(_ProjectionDecoder):
                  graph_generator, normalize_by_dim=None,
                  numerator_red='logsumexp', denominator_red='logsumexp',
                  embedder='LutLinear', embedder_kwargs={}, decode_beam=None,
-                 decode_lattice_beam=None, decode_nbest=1, decode_confidence=False, **kwargs):
+                 decode_lattice_beam=None, decode_nbest=1, decode_confidence=False,
+                 decode_nbest_device=False, **kwargs):
         super(FSTDecoder, self).__init__(**kwargs)
         # decode_beam: None = the exact every-state Viterbi below; a number = the beam-pruned
         # token-passing search (att_speech/wfst_decode.py) over the same graph with that beam
@@ -613,12 +614,16 @@ class FSTDecoder(_ProjectionDecoder):
         # decode_confidence: decode() also adds 'word_confidence': per utterance one posterior for
         # each label of the lattice's best path at the search scale (att_speech/lattice_dp.py:
         # posteriors().word_posteriors(window=0)); the lattice then stays on the device
+        # decode_nbest_device: 'nbest' comes from the lattices where the search left them
+        # (DeviceLatticeBatch.nbest, one launch per batch) instead of Lattice.nbest per utterance
+        # on the host: the same costs; sequences that tie at the last place may differ
         if decode_lattice_beam is not None and decode_beam is None:
             raise ValueError("decode_lattice_beam needs decode_beam: the lattice comes from the beam search")
         if decode_confidence and decode_lattice_beam is None:
             raise ValueError("decode_confidence needs decode_lattice_beam: the posteriors are the lattice's")
         self.decode_beam, self.decode_confidence = decode_beam, bool(decode_confidence)
         self.decode_lattice_beam, self.decode_nbest = decode_lattice_beam, int(decode_nbest)
+        self.decode_nbest_device = bool(decode_nbest_device)
         self._decoding_graph = None
         gg = utils.contruct_from_kwargs(
             graph_generator, 'att_speech.fst_utils',
@@ -726,14 +731,18 @@ class FSTDecoder(_ProjectionDecoder):
             res = wfst_decode.decode_graph(logits.detach().float(), encoded_lens, self._decoding_graph,
                                            beam=float(self.decode_beam))
             ret = {'decoded': res['words'], 'logits': logits}   # the labels on the winning arcs
-            if self.decode_lattice_beam is not None and self.decode_confidence:
+            if self.decode_lattice_beam is not None and (self.decode_confidence or self.decode_nbest_device):
                 from att_speech import lattice_dp
                 batch, _ = lattice_dp.decode_lattice_device(
                     logits.detach().float(), encoded_lens, self._decoding_graph, beam=float(self.decode_beam),
                     lattice_beam=float(self.decode_lattice_beam))
-                ret['nbest'] = [lat.nbest(self.decode_nbest) for lat in batch.lattices()]
-                ret['word_confidence'] = [[p for _, _, p in row]
-                                          for row in batch.posteriors().word_posteriors(window=0)]
+                if self.decode_nbest_device:
+                    ret['nbest'] = batch.nbest(self.decode_nbest)
+                else:
+                    ret['nbest'] = [lat.nbest(self.decode_nbest) for lat in batch.lattices()]
+                if self.decode_confidence:
+                    ret['word_confidence'] = [[p for _, _, p in row]
+                                              for row in batch.posteriors().word_posteriors(window=0)]
             elif self.decode_lattice_beam is not None:
                 from att_speech import wfst_lattice
                 lats, _ = wfst_lattice.decode_lattice(

@@ -176,6 +176,40 @@ class Lattice(object):
         return [w for w, _ in self.nbest(n, **kw)]
 
 
+NBEST_HASH_MUL = 0x9E3779B97F4A7C15     # H(o, h) = h * NBEST_HASH_MUL + o + 1 mod 2^64: LatticeBatch.nbest
+
+
+class _Entries(object):
+    """the n-best entries of all nodes, one after another, in arrays that grow"""
+
+    NAMES = (('c', np.float64), ('ln', np.int64), ('h', np.uint64), ('arc', np.int64), ('rank', np.int64))
+
+    def __init__(self):
+        self.used = 0
+        for name, dtype in self.NAMES:
+            setattr(self, name, np.zeros(1024, dtype))
+
+    def append(self, *columns):
+        k = len(columns[0])
+        for (name, dtype), col in zip(self.NAMES, columns):
+            a = getattr(self, name)
+            if self.used + k > len(a):
+                a = np.concatenate([a, np.zeros(max(len(a), k), dtype)])
+                setattr(self, name, a)
+            a[self.used:self.used + k] = col
+        self.used += k
+
+
+def nbest_lists(num_utterances, utt, words, cost):
+    """entries (utterance, words, cost) -> per utterance [(words, cost)] sorted by (cost, words)"""
+    out = [[] for _ in range(num_utterances)]
+    for b, w, c in zip(utt, words, cost):
+        out[b].append((w, c))
+    for row in out:
+        row.sort(key=lambda entry: (entry[1], entry[0]))
+    return out
+
+
 class LatticeBatch(object):
     """The lattices of many utterances over one graph, laid end to end, so that one dynamic
     programme serves them all: a sweep over acoustic scales builds this once and calls best_paths
@@ -205,6 +239,7 @@ class LatticeBatch(object):
         at_n = self.time == frames[self.n_utt]
         # the unscaled cost of stopping at a node (+inf: not an end node)
         self.end = np.where(at_n, np.where(reached[self.n_utt], g.final[self.state].astype(np.float64), 0.0), INF)
+        self.free_end = at_n & ~reached[self.n_utt]      # end nodes of a partial lattice: 0 whatever the LM scale
         # arcs grouped by the (time, epsilon rank) of their source, ascending: a node's cost is final
         # before its arcs are relaxed
         key = self.time[self.src] * (g.num_ranks + 1) + g.rank[self.state[self.src]]
@@ -283,6 +318,113 @@ class LatticeBatch(object):
                 arcs[wu[i]].append(int(wa[i]))
         return ([(words[b], float(best[b]), float(gc[b]), float(ac[b])) if best[b] < INF else none
                  for b in range(B)], [arcs[b] if best[b] < INF else [] for b in range(B)])
+
+    def nbest(self, n, acoustic_scale=None, lm_scale=1.0):
+        """The n cheapest DISTINCT word sequences of every lattice: one [(words, cost)] per utterance,
+        sorted by (cost, words).  The k-best dynamic programme of DESIGN.md section 4.22, and the
+        numpy twin of asr_lattice_nbest_f64, operation for operation, so both give the same bits.
+
+        Backwards over the (time, epsilon rank) levels every node v keeps a list of at most n
+        entries (c, len, h, arc, rank): the cost of a word suffix from v to an end, its number of
+        words, a 64-bit hash of it, the out-arc taken (-1: stop at v) and the index into the list
+        of that arc's destination.  Candidates of v: the stop entry (e(v), 0, 0, -1, 0) when
+        e(v) < inf (e as in Lattice._end_costs), and for every out-arc j and entry r of its
+        destination (fl(x_j + c_r), len_r + [olabel_j != 0], H(olabel_j, h_r), j, r), dropped unless
+        the cost is < inf (NaN goes too); x_j = fl(fl(lm w) - fl(sc lp)) as in best_paths.
+        H(o, h) = h * 0x9E3779B97F4A7C15 + o + 1 mod 2^64 for o != 0, h otherwise; the empty suffix
+        hashes to 0.  The candidates are ordered by (c, len, h, arc, rank); of those with equal
+        (len, h) the first survives; the list is the first n survivors.
+
+        Read-out: the start node's entries are followed forwards along (arc, rank), the non-zero
+        output labels collected, and the cost summed forwards (g = 0; g = fl(g + x_j); fl(g + e)) as
+        Lattice.nbest and best_paths sum it.
+
+        Two suffixes count as the same sequence iff (len, h) agree: a 64-bit hash identity.  A
+        collision would drop one of two different sequences from a list and nothing else.  Against
+        Lattice.nbest: the same costs; sequences that tie at the n-th cost are cut by (len, hash)
+        here and by the words there."""
+        B = len(self.lattices)
+        n = int(n)
+        N = len(self.time) if B else 0
+        if n < 1 or not N:
+            return [[] for _ in range(B)]
+        g = self.graph
+        sc = self.scale if acoustic_scale is None else float(acoustic_scale)
+        lm = float(lm_scale)
+        mul, one = np.uint64(NBEST_HASH_MUL), np.uint64(1)
+        with np.errstate(invalid='ignore', over='ignore'):
+            x = lm * self.w - sc * self.lp
+            e = np.where(self.end < INF, np.where(self.free_end, 0.0, lm * np.where(self.end < INF, self.end, 0.0)),
+                         INF)
+            level = self.time * (g.num_ranks + 1) + g.rank[self.state]
+            order = np.argsort(-level, kind='stable')
+            cuts = np.nonzero(np.r_[True, level[order][1:] != level[order][:-1]])[0]
+            out_ptr = np.searchsorted(self.src, np.arange(N + 1))
+            off, cnt = np.zeros(N, np.int64), np.zeros(N, np.int64)
+            ent = _Entries()
+            for a, b in zip(cuts, list(cuts[1:]) + [N]):
+                V = order[a:b]
+                arcs, owner = _ranges(out_ptr[V], out_ptr[V + 1])
+                d = self.dst[arcs]
+                pos, which = _ranges(off[d], off[d] + cnt[d])
+                ca, ol = arcs[which], self.ol[arcs[which]]
+                word = ol != 0
+                c = x[ca] + ent.c[pos]
+                h = np.where(word, ent.h[pos] * mul + ol.astype(np.int64).astype(np.uint64) + one, ent.h[pos])
+                ok = c < INF
+                stop = V[e[V] < INF]
+                zero = np.zeros(len(stop), np.int64)
+                node = np.r_[V[owner[which]][ok], stop]
+                c = np.r_[c[ok], e[stop]]
+                ln = np.r_[(ent.ln[pos] + word)[ok], zero]
+                h = np.r_[h[ok], zero.astype(np.uint64)]
+                arc = np.r_[ca[ok], zero - 1]
+                rank = np.r_[(pos - off[d][which])[ok], zero]
+                o = np.lexsort((rank, arc, h, ln, c, node))
+                node, c, ln, h, arc, rank = (v[o] for v in (node, c, ln, h, arc, rank))
+                # of equal (node, len, h) the first in that order; lexsort is stable
+                o = np.lexsort((h, ln, node))
+                same = (node[o][1:] == node[o][:-1]) & (ln[o][1:] == ln[o][:-1]) & (h[o][1:] == h[o][:-1])
+                keep = np.zeros(len(o), bool)
+                keep[o[np.r_[True, ~same][:len(o)]]] = True
+                node, c, ln, h, arc, rank = (v[keep] for v in (node, c, ln, h, arc, rank))
+                first = np.nonzero(np.r_[True, node[1:] != node[:-1]][:len(node)])[0]
+                run = np.diff(np.r_[first, len(node)])
+                keep = np.arange(len(node)) - np.repeat(first, run) < n
+                u, at, k = np.unique(node[keep], return_index=True, return_counts=True)
+                off[u], cnt[u] = ent.used + at, k
+                ent.append(c[keep], ln[keep], h[keep], arc[keep], rank[keep])
+            # read-out: every entry of every start node, all chains at once
+            start = np.full(B, N, np.int64)
+            at = np.nonzero(self.start)[0]
+            np.minimum.at(start, self.n_utt[at], at)
+            utts = np.nonzero(start < N)[0]
+            pos, which = _ranges(off[start[utts]], off[start[utts]] + cnt[start[utts]])
+            utt = utts[which]
+            node = start[utt]
+            total, cost = np.zeros(len(pos)), np.full(len(pos), INF)
+            live = np.ones(len(pos), bool)
+            w_ent, w_lab = [], []
+            for _ in range(len(cuts) + 1):              # a path has at most one arc per level
+                arc = ent.arc[pos]
+                ends = live & (arc < 0)
+                cost[ends] = total[ends] + e[node[ends]]
+                live = live & (arc >= 0)
+                i = np.nonzero(live)[0]
+                if not len(i):
+                    break
+                j = arc[i]
+                total[i] = total[i] + x[j]
+                has = self.ol[j] != 0
+                w_ent.append(i[has])
+                w_lab.append(self.ol[j][has])
+                pos[i] = off[self.dst[j]] + ent.rank[pos[i]]
+                node[i] = self.dst[j]
+        words = [[] for _ in range(len(pos))]
+        if w_ent:                                       # step by step: every entry's words in path order
+            for i, lab in zip(np.concatenate(w_ent).tolist(), np.concatenate(w_lab).tolist()):
+                words[i].append(int(lab))
+        return nbest_lists(B, utt.tolist(), words, cost.tolist())
 
     def posteriors(self, acoustic_scale=None, lm_scale=1.0):
         """Arc and node posteriors of every lattice under the path weights exp(-(sum of x + lm_scale *

@@ -1,5 +1,6 @@
 // Dynamic programmes over a batch of pruned lattices that stays on the device (include/asr_amd.h:
-// asr_lattice_bestpath_f64, asr_lattice_posterior_f64 and their _supported / _workspace_bytes).
+// asr_lattice_bestpath_f64, asr_lattice_posterior_f64, asr_lattice_nbest_f64 and their _supported /
+// _workspace_bytes).
 //
 // The lattices are those of asr_wfst_lattice_f32 in the canonical form of DESIGN.md section 4.20,
 // laid end to end: nodes by (utterance, time, state), arcs by (utterance, source node, graph arc).
@@ -16,8 +17,12 @@
 //   posterior  one workgroup per utterance: forward over the levels upwards (in-arcs), backward
 //              downwards (out-arcs), each node reduced by its one owner lane as max-then-sum
 //              logsumexp in the stored order; no atomics, so two runs give the same bits.
+//   nbest      one workgroup per utterance, levels downwards: a wave owns a node and merges the lists of
+//              its out-arcs' destinations, a lane per arc, into the node's n cheapest distinct word
+//              suffixes by wave-wide minima of a five-field key; then a lane per entry of the start
+//              node walks its chain forwards.  Defined by a total order, so two runs give the same bits.
 //
-// Both synchronise with workgroup barriers only.  Every node, arc, level and graph index read from
+// All synchronise with workgroup barriers only.  Every node, arc, level and graph index read from
 // memory is range-checked before it is used (the tensors may come from a caller): a violation raises
 // the utterance's status word and ends its workgroup.  Every loop is bounded by the counts passed in.
 #include "common.h"
@@ -406,6 +411,259 @@ __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q)
     if (tid == 0) q.log_z[b] = z, q.out_status[b] = dead ? 1 : 0;
 }
 
+// ---- n-best lists (asr_lattice_nbest_f64) --------------------------------
+// A list entry is 28 bytes of workspace: cost f64, suffix hash u64, word count, out-arc and rank i32;
+// a node has n entries and one i32 count.  One wave owns a node; a lane owns an out-arc of it (64 arcs
+// a round) and, of the list under construction, the entry of its own index: hence n <= 64.
+constexpr int NBEST_MAX = 64;
+constexpr uint64_t NBEST_HASH_MUL = 0x9E3779B97F4A7C15ull;
+
+struct NbestArgs {
+    Lat t;
+    int n;
+    double ac_scale, lm_scale;              // ac_scale NaN: the utterance's own
+    double *ec;                             // workspace: [nodes of the launch][n] each, ecnt [nodes]
+    uint64_t *eh;
+    int32_t *elen, *earc, *erank, *ecnt;
+    int32_t *out_count;                     // [B]
+    double *out_cost;                       // [B][n]
+    int32_t *out_nwords, *out_words, *out_status;       // [B][n], [n L], [B]
+};
+
+// the order of the candidates: (cost, words, hash, (arc + 1, rank)); costs are never NaN here
+struct NKey {
+    double c;
+    uint64_t h, ar;
+    int32_t len, valid;
+};
+
+__device__ __forceinline__ bool key_less(const NKey &a, const NKey &b) {
+    if (a.c != b.c) return a.c < b.c;
+    if (a.len != b.len) return a.len < b.len;
+    if (a.h != b.h) return a.h < b.h;
+    return a.ar < b.ar;
+}
+
+__device__ __forceinline__ NKey key_from_lane(const NKey &k, int src) {
+    NKey o;
+    o.c = __shfl(k.c, src);
+    o.h = (uint64_t)__shfl((unsigned long long)k.h, src);
+    o.ar = (uint64_t)__shfl((unsigned long long)k.ar, src);
+    o.len = __shfl(k.len, src);
+    o.valid = __shfl(k.valid, src);
+    return o;
+}
+
+// the smallest valid key of the wave, in every lane
+__device__ __forceinline__ NKey wave_min(NKey k) {
+    for (int m = 1; m < 64; m <<= 1) {
+        NKey o;
+        o.c = __shfl_xor(k.c, m);
+        o.h = (uint64_t)__shfl_xor((unsigned long long)k.h, m);
+        o.ar = (uint64_t)__shfl_xor((unsigned long long)k.ar, m);
+        o.len = __shfl_xor(k.len, m);
+        o.valid = __shfl_xor(k.valid, m);
+        if (o.valid && (!k.valid || key_less(o, k))) k = o;
+    }
+    return k;
+}
+
+// fl(lm end(v)) as Lattice._end_costs has it: 0 at the last time of a partial lattice
+__device__ __forceinline__ double scaled_end(const Lat &t, int64_t v, int frames, int reached, double lm, bool &bad) {
+    if (t.time[v] != frames) return DINF;
+    if (!reached) return 0.0;
+    const int s = t.state[v];
+    if (s < 0 || s >= t.S) {
+        bad = true;
+        return DINF;
+    }
+    return lm * (double)t.fin[s];
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void lattice_nbest_kernel(const NbestArgs q) {
+    const Lat &t = q.t;
+    constexpr int NW = NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = t.b_begin + (int)blockIdx.x;
+    const int n = q.n;
+    __shared__ unsigned long long s_start;
+    if (tid == 0) s_start = ~0ull;
+    __syncthreads();
+    const Span sp = span_of(t, b);
+    bool fail = !sp.ok;
+    if (!fail) fail = t.level_ptr[sp.l0] != sp.n0 || t.level_ptr[sp.l1] != sp.n1;
+    if (fail) {
+        if (tid == 0) q.out_count[b] = 0, q.out_status[b] = 1;
+        return;
+    }
+    double sc = q.ac_scale;
+    if (sc != sc) sc = t.own_scale[b];
+    const double lm = q.lm_scale;
+    const int frames = t.frames[b], reached = t.reached[b];
+    const int64_t nlev = sp.l1 - sp.l0;
+    double *const ec = q.ec - t.n_begin * n;            // indexed by batch node * n + rank
+    uint64_t *const eh = q.eh - t.n_begin * n;
+    int32_t *const elen = q.elen - t.n_begin * n, *const earc = q.earc - t.n_begin * n;
+    int32_t *const erank = q.erank - t.n_begin * n, *const ecnt = q.ecnt - t.n_begin;
+    bool bad = false, dead = false;
+    for (int64_t l = sp.l1 - 1; l >= sp.l0; --l) {      // levels downwards: the lists above are final
+        const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
+        if (e0 < sp.n0 || e0 > e1 || e1 > sp.n1) {
+            bad = true;
+        } else {
+            for (int64_t e = e0 + wave; e < e1; e += NW) {      // everything here is uniform in the wave
+                const int64_t v = t.level_node[e];
+                if (v < sp.n0 || v >= sp.n1 || t.level[v] != l) {
+                    bad = true;
+                    continue;
+                }
+                if (lane == 0 && t.time[v] == 0 && t.state[v] == t.start) atomicMin(&s_start, (unsigned long long)v);
+                const int64_t j0 = t.out_ptr[v], j1 = t.out_ptr[v + 1];
+                if (j0 < sp.a0 || j0 > j1 || j1 > sp.a1) {
+                    bad = true;
+                    continue;
+                }
+                // the list so far: entry i in lane i.  It starts as the stop entry alone.
+                NKey cur;
+                cur.c = scaled_end(t, v, frames, reached, lm, bad);
+                cur.h = 0, cur.ar = 0, cur.len = 0;
+                int m = cur.c < DINF ? 1 : 0;
+                cur.valid = lane < m;
+                for (int64_t jb = j0; jb < j1; jb += 64) {      // 64 out-arcs a round against that list
+                    const int64_t a = jb + lane;
+                    bool has = a < j1;
+                    double x = DINF;
+                    int32_t olab = 0;
+                    int64_t dbase = 0;
+                    int dcnt = 0, lo = 0;
+                    if (has) {
+                        const int64_t d = sp.n0 + t.dst[a], g = t.arc[a];
+                        if (sp.n0 + t.src[a] != v || d < sp.n0 || d >= sp.n1 || g < 0 || g >= t.G) {
+                            bad = true, has = false;
+                        } else {
+                            const int32_t ld = t.level[d];
+                            if (ld <= l || ld >= sp.l1) {       // the level must rise: list(d) is final
+                                bad = true, has = false;
+                            } else {
+                                x = arc_cost(lm, sc, t.w[g], t.lp[a]);
+                                olab = t.ol[g];
+                                dcnt = ecnt[d];
+                                dbase = d * n;
+                                if (dcnt < 0 || dcnt > n) bad = true, has = false;
+                                if (!(x < DINF)) has = false;   // +inf or NaN: no candidate survives
+                            }
+                        }
+                    }
+                    const uint64_t arhi = (uint64_t)(a - sp.a0 + 1) << 32;
+                    NKey last, best;
+                    last.valid = 0, best.valid = 0;
+                    // this arc's smallest candidate above `last`.  c' = fl(x + c_r) does not fall as r
+                    // grows, so the ranks whose c' is below last.c are spent for good (lo), and the scan
+                    // ends at the first c' above the best so far; equal c' are compared in full.
+                    auto rescan = [&]() {
+                        best.valid = 0;
+                        for (int r = lo; r < dcnt; ++r) {
+                            const double c = x + ec[dbase + r];
+                            if (!(c < DINF)) break;
+                            if (last.valid && c < last.c) {
+                                lo = r + 1;
+                                continue;
+                            }
+                            if (best.valid && c > best.c) break;
+                            NKey k;
+                            k.c = c;
+                            k.len = elen[dbase + r] + (olab != 0 ? 1 : 0);
+                            const uint64_t h = eh[dbase + r];
+                            k.h = olab != 0 ? h * NBEST_HASH_MUL + (uint64_t)(int64_t)olab + 1 : h;
+                            k.ar = arhi | (uint32_t)r;
+                            k.valid = 1;
+                            if (last.valid && !key_less(last, k)) continue;
+                            if (!best.valid || key_less(k, best)) best = k;
+                        }
+                    };
+                    if (has) rescan();
+                    NKey out;                   // the merged list: entry i in lane i
+                    out.c = DINF, out.h = 0, out.ar = 0, out.len = 0, out.valid = 0;
+                    int mo = 0, po = 0;
+                    for (int it = 0; it < 65 * n && mo < n; ++it) {     // every turn spends a candidate
+                        NKey w = wave_min(best);
+                        bool old = false;
+                        if (po < m) {
+                            const NKey head = key_from_lane(cur, po);
+                            if (!w.valid || key_less(head, w)) w = head, old = true;
+                        }
+                        if (!w.valid) break;
+                        last = w;
+                        if (old)
+                            ++po;
+                        else if (has && best.valid && best.ar == w.ar)
+                            rescan();
+                        const bool dup = lane < mo && out.len == w.len && out.h == w.h;
+                        if (__ballot(dup) == 0ull) {
+                            if (lane == mo) out = w;
+                            ++mo;
+                        }
+                    }
+                    cur = out, m = mo;
+                }
+                if (lane < m) {
+                    const int64_t i = v * n + lane;
+                    ec[i] = cur.c, eh[i] = cur.h, elen[i] = cur.len;
+                    earc[i] = (int32_t)(cur.ar >> 32) - 1;
+                    erank[i] = (int32_t)(cur.ar & 0xFFFFFFFFull);
+                }
+                if (lane == 0) ecnt[v] = m;
+            }
+        }
+        dead = __syncthreads_or(bad) != 0;      // also makes the level's lists visible to every wave
+        if (dead) break;
+    }
+    __syncthreads();
+    // read-out: lane i of the first wave follows entry i of the start node forwards
+    const unsigned long long st = s_start;
+    int count = 0;
+    if (!dead && st >= (unsigned long long)sp.n0 && st < (unsigned long long)sp.n1) {
+        count = ecnt[st];
+        if (count < 0 || count > n) bad = true, count = 0;
+    }
+    if (wave == 0 && lane < count) {
+        int64_t v = (int64_t)st;
+        int r = lane, nw = 0;
+        double g = 0.0, cost = DINF;
+        bool done = false;
+        int32_t *const words = q.out_words + (int64_t)n * sp.l0 + (int64_t)lane * nlev;
+        for (int64_t step = 0; step <= nlev; ++step) {          // a path has at most one arc per level
+            const int32_t al = earc[v * n + r];
+            if (al < 0) {
+                cost = g + scaled_end(t, v, frames, reached, lm, bad);
+                done = true;
+                break;
+            }
+            const int64_t a = sp.a0 + al;
+            if (a < t.out_ptr[v] || a >= t.out_ptr[v + 1] || a >= sp.a1) break;
+            const int64_t d = sp.n0 + t.dst[a], ga = t.arc[a];
+            if (d < sp.n0 || d >= sp.n1 || ga < 0 || ga >= t.G) break;
+            const int32_t ld = t.level[d];
+            if (ld <= t.level[v] || ld >= sp.l1) break;
+            const int32_t rk = erank[v * n + r];
+            if (rk < 0 || rk >= ecnt[d] || ecnt[d] > n) break;
+            g = g + arc_cost(lm, sc, t.w[ga], t.lp[a]);
+            const int32_t word = t.ol[ga];
+            if (word != 0) {
+                if (nw >= nlev) break;
+                words[nw++] = word;
+            }
+            v = d, r = rk;
+        }
+        if (!done) bad = true;
+        q.out_cost[(int64_t)b * n + lane] = cost;
+        q.out_nwords[(int64_t)b * n + lane] = done ? nw : 0;
+    }
+    dead = __syncthreads_or(bad) != 0 || dead;
+    if (tid == 0) q.out_count[b] = dead ? 0 : count, q.out_status[b] = dead ? 1 : 0;
+}
+
 bool sizes_ok(int64_t N, int64_t A, int64_t L) {
     const int64_t lim = ((int64_t)1 << 31) - 1;
     return N >= 0 && A >= 0 && L >= 0 && N < lim && A < lim && L < lim;
@@ -546,6 +804,65 @@ extern "C" int asr_lattice_posterior_f64(
     case 256: hipLaunchKernelGGL(lattice_posterior_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, q); break;
     case 128: hipLaunchKernelGGL(lattice_posterior_kernel<128>, grid, dim3(128), 0, (hipStream_t)stream, q); break;
     default: hipLaunchKernelGGL(lattice_posterior_kernel<64>, grid, dim3(64), 0, (hipStream_t)stream, q); break;
+    }
+    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+}
+
+extern "C" int asr_lattice_nbest_supported(int64_t N, int64_t A, int64_t L, int n) {
+    return sizes_ok(N, A, L) && n >= 1 && n <= NBEST_MAX ? 1 : 0;
+}
+
+extern "C" int64_t asr_lattice_nbest_workspace_bytes(int64_t num_nodes, int n) {
+    if (num_nodes < 0 || n < 1 || n > NBEST_MAX || !sizes_ok(num_nodes, 0, 0)) return 0;
+    const int64_t e = num_nodes * n;
+    return 2 * up16(e * 8) + 3 * up16(e * 4) + up16(num_nodes * 4) + 16;
+}
+
+extern "C" int asr_lattice_nbest_f64(
+    int B, int b_begin, int b_count, int n, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
+    const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
+    const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
+    const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
+    double acoustic_scale, double lm_scale, int64_t num_states, int64_t num_graph_arcs, const float *arc_weight,
+    const int32_t *arc_olabel, const float *final_cost, int start, int threads, int32_t *out_count,
+    double *out_cost, int32_t *out_num_words, int32_t *out_words, int32_t *out_status, void *workspace,
+    int64_t workspace_bytes, void *stream) {
+    NbestArgs q;
+    const int rc = fill(q.t, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off, node_off, arc_off,
+                        level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc, lat_lp, level_ptr,
+                        level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final, own_scale, num_states,
+                        num_graph_arcs, arc_weight, arc_olabel, final_cost, start);
+    if (rc != ASR_OK) return rc;
+    if (n < 1 || !threads_ok(threads)) return ASR_EINVAL;
+    if (n > NBEST_MAX) return ASR_EUNSUPPORTED;
+    if (b_count == 0) return ASR_OK;
+    if (!out_count || !out_cost || !out_num_words || !out_status || (L > 0 && !out_words)) return ASR_EINVAL;
+    const int64_t nodes = h_node_off[b_begin + b_count] - h_node_off[b_begin];
+    const int64_t need = asr_lattice_nbest_workspace_bytes(nodes, n);
+    if (need <= 0 || !workspace || workspace_bytes < need) return ASR_EINVAL;
+    const int64_t e = nodes * n;
+    uint8_t *p = (uint8_t *)workspace;
+    q.n = n;
+    q.ac_scale = acoustic_scale;
+    q.lm_scale = lm_scale;
+    q.ec = (double *)p, p += up16(e * 8);
+    q.eh = (uint64_t *)p, p += up16(e * 8);
+    q.elen = (int32_t *)p, p += up16(e * 4);
+    q.earc = (int32_t *)p, p += up16(e * 4);
+    q.erank = (int32_t *)p, p += up16(e * 4);
+    q.ecnt = (int32_t *)p;
+    q.out_count = out_count;
+    q.out_cost = out_cost;
+    q.out_nwords = out_num_words;
+    q.out_words = out_words;
+    q.out_status = out_status;
+    const dim3 grid((unsigned)b_count);
+    switch (threads) {                          // 0: four waves, four nodes of a level at a time (section 4.22)
+    case 64: hipLaunchKernelGGL(lattice_nbest_kernel<64>, grid, dim3(64), 0, (hipStream_t)stream, q); break;
+    case 128: hipLaunchKernelGGL(lattice_nbest_kernel<128>, grid, dim3(128), 0, (hipStream_t)stream, q); break;
+    default: hipLaunchKernelGGL(lattice_nbest_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, q); break;
     }
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
 }

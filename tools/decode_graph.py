@@ -4,7 +4,7 @@ reference's scoring recipe (egs/wsj/ctc_kaldi_decode.sh:141-147) without Kaldi.
 
     python tools/decode_graph.py LOGPROBS.ark GRAPH.fst [--words words.txt] [--beam 16]
         [--acoustic-scale 1.0] [--batch 64] [--device cuda:0|cpu] [--out FILE]
-        [--lattice-beam X --nbest N [--acwt-sweep LO:HI:STEP] [--post OUT.npz]]
+        [--lattice-beam X --nbest N [--device-nbest] [--acwt-sweep LO:HI:STEP] [--post OUT.npz]]
 
 LOGPROBS.ark: the float-matrix archive att_speech.ctc_forward writes (one [frames, classes] matrix
 per utterance).  GRAPH.fst: an OpenFst binary (vector/standard, plain or gzip) or an AT&T text
@@ -14,7 +14,9 @@ archive order: the integer transcript decode-faster writes to `ark,t:`, or symbo
 
 With --lattice-beam the search keeps a lattice (att_speech.wfst_lattice.decode_lattice:
 latgen-faster) and the output is its n-best list, `uttid-k cost w1 w2 ...` for k = 1..N, cheapest
-first.  With --acwt-sweep as well, the one search (at --acoustic-scale) is re-ranked for every scale
+first.  With --device-nbest the lists come from the lattices where the search left them
+(DeviceLatticeBatch.nbest: one launch per batch; the same costs, ties at the last place may fall to
+other sequences).  With --acwt-sweep as well, the one search (at --acoustic-scale) is re-ranked for every scale
 LO, LO + STEP, ..., HI, which the recipe does with one decode-faster run per scale
 (egs/wsj/ctc_kaldi_decode.sh:160-163): lines `scale uttid cost w1 w2 ...`, scale by scale.  The
 lattices stay on the device and all scales are one call (att_speech.lattice_dp).  With --post the
@@ -67,13 +69,25 @@ def _tokens(table, words):
 
 
 def write_nbest(graph, utts, path, beam, lattice_beam, nbest, acoustic_scale=1.0, allow_partial=True,
-                device='cpu', batch=64, table=None):
-    """`uttid-k cost w1 w2 ...`: the nbest cheapest distinct word sequences of every utterance"""
+                device='cpu', batch=64, table=None, device_nbest=False):
+    """`uttid-k cost w1 w2 ...`: the nbest cheapest distinct word sequences of every utterance;
+    device_nbest: listed by DeviceLatticeBatch.nbest, a batch at a time"""
+    kw = dict(beam=beam, lattice_beam=lattice_beam, acoustic_scale=acoustic_scale, allow_partial=allow_partial)
+
+    def lists():
+        if not device_nbest:
+            for key, lat in _lattices(graph, utts, device, batch, **kw):
+                yield key, lat.nbest(nbest)
+            return
+        from att_speech.lattice_dp import decode_lattice_device
+        for keys, lp, lens in _batches(utts, batch):
+            every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, **kw)
+            for key, row in zip(keys, every.nbest(nbest)):
+                yield key, row
     out = open(path, 'w') if path else sys.stdout
     try:
-        for key, lat in _lattices(graph, utts, device, batch, beam=beam, lattice_beam=lattice_beam,
-                                  acoustic_scale=acoustic_scale, allow_partial=allow_partial):
-            for k, (words, cost) in enumerate(lat.nbest(nbest)):
+        for key, row in lists():
+            for k, (words, cost) in enumerate(row):
                 out.write(' '.join(['%s-%d' % (key, k + 1), '%.6f' % cost] + _tokens(table, words)) + '\n')
     finally:
         if path:
@@ -129,11 +143,13 @@ def main(argv=None):
     ap.add_argument('--out', default=None, help='default: standard output')
     ap.add_argument('--lattice-beam', type=float, default=None, help='keep a lattice this wide; write its n-best')
     ap.add_argument('--nbest', type=int, default=1)
+    ap.add_argument('--device-nbest', action='store_true',
+                    help='list the n-best on the device, a batch per launch (DeviceLatticeBatch.nbest)')
     ap.add_argument('--acwt-sweep', default=None, help='LO:HI:STEP: the 1-best per acoustic scale from one search')
     ap.add_argument('--post', default=None, help='OUT.npz: frame-level class posteriors of every lattice')
     a = ap.parse_args(argv)
-    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post):
-        ap.error('--nbest, --acwt-sweep and --post need --lattice-beam')
+    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post or a.device_nbest):
+        ap.error('--nbest, --device-nbest, --acwt-sweep and --post need --lattice-beam')
     from att_speech import wfst_decode
     from att_speech.ctc_forward import read_kaldi_float_matrices
     from att_speech.lm_fst import SymbolTable
@@ -151,7 +167,7 @@ def main(argv=None):
         elif a.acwt_sweep:
             write_sweep(graph, utts, a.out, scales=parse_sweep(a.acwt_sweep), **kw)
         else:
-            write_nbest(graph, utts, a.out, nbest=a.nbest, **kw)
+            write_nbest(graph, utts, a.out, nbest=a.nbest, device_nbest=a.device_nbest, **kw)
         return
     out = open(a.out, 'w') if a.out else sys.stdout
     try:
