@@ -1367,6 +1367,81 @@ int asr_lattice_nbest_f64(
     double *out_cost, int32_t *out_num_words, int32_t *out_words, int32_t *out_status, void *workspace,
     int64_t workspace_bytes, void *stream);
 
+/*
+ * asr_lattice_mbr_f64: minimum-Bayes-risk decoding of every lattice of such a batch in one launch
+ * (csrc/lattice_dp.hip; Xu, Povey, Mangu, Zhu 2011, Kaldi's lattice-mbr-decode;
+ * LatticeBatch.mbr of att_speech/wfst_lattice.py is its numpy twin and gives the same results with ==).
+ * Additions: the ABI version stays 24.  The batch, b_begin / b_count, x and end(v) as above; threads: 64,
+ * 128 or 256 lanes per workgroup, 0 = 256; acoustic_scale NaN: own_scale.
+ *
+ * Lattice model, per utterance.  A virtual end node E; every node v with end(v) < inf has a stop arc
+ * v -> E without a word; an arc's word is the olabel of its graph arc, 0 = no word.  The start node is
+ * the node (time 0, state `start`); arcs into it are ignored.
+ * Conditional posteriors: pi_j = exp((fwd(src_j) - x_j) - fwd(dst_j)), pi_stop(v) = exp((fwd(v) -
+ *   fl(lm end(v))) - log_z), fwd the forward score of asr_lattice_posterior_f64 and log_z the log-sum of
+ *   the stop terms (one lane, node order, max then sum); 0 where a term is infinite or the value is not
+ *   > 0.  arc_cond [A] / end_cond [N] f64 give them; NULL (either): computed here as phase 0.
+ * Hypothesis w_1..w_Q in slot form r_1..r_S, S = 2Q + 1: r_q = 0 at odd q (gaps), r_2k = w_k.
+ * Losses, delta = 1e-5: sub(w, r) = 0 if w == r else 1 + delta; ins(w) = 0 if w == 0 else 1 + delta;
+ *   del(r) = 0 if r == 0 else 1.
+ * Forward: alpha'(s, 0) = 0, alpha'(s, q) = alpha'(s, q-1) + del(r_q) at the start node s; for every
+ *   other node v (E last) and every in-arc (u -> v, w, pi) with pi > 0:
+ *     a(0) = alpha'(u, 0) + ins(w),
+ *     a(q) = min(A1 = alpha'(u, q-1) + sub(w, r_q), A2 = alpha'(u, q) + ins(w), A3 = a(q-1) + del(r_q)),
+ *     alpha'(v, q) = sum over the in-arcs of pi a(q);   risk = alpha'(E, S).
+ * Backward: beta'(E, S) = 1; nodes by descending level (E first); per in-arc, q = S .. 1:
+ *     b(q) += pi beta'(v, q); case 1 (A1 <= A2 and A1 <= A3): beta'(u, q-1) += b(q), gamma(q, w) += b(q),
+ *     tau(q, w) += b(q) time(v); case 2 (else A2 <= A3): beta'(u, q) += b(q); case 3: b(q-1) += b(q),
+ *     gamma(q, 0) += b(q); finally b(0) += pi beta'(v, 0), beta'(u, 0) += b(0).  At the start node case 3
+ *     alone is applied to beta'(s, .).  For every slot the gamma(q, .) sum to 1.
+ * Update: r_q <- argmax_w gamma(q, w); among equal maxima the current r_q if it is one, else the smallest
+ *   label; zeros dropped, gaps re-inserted.
+ * Iteration: start from init_words (utterance b: init_num_words[b] words at init_words + b max_words) or,
+ *   both NULL, from the tropical best path under the tie rule of asr_lattice_bestpath_f64; evaluate,
+ *   update; stop when the words did not change or after max(1, max_iterations) evaluations
+ *   (max_iterations = 0 scores the given sentences unchanged).  The result is the last EVALUATED
+ *   hypothesis's: confidence of word k = gamma(2k, w_k), frame = tau / gamma to the nearest integer.
+ * Arithmetic (the order of additions cannot matter): alpha' and a are int64 at 2^-40 (1 = 2^40, delta =
+ *   10995116); beta', b, gamma int64 at 2^-52; every product is llrint(pi (double)v), round-half-even,
+ *   uncontracted; tau adds (b >> 12) time(v) and frame = rint((double)tau / (double)(gamma >> 12)) (0 when
+ *   gamma >> 12 is 0); minima, cases and the argmax are integer comparisons, entries with b = 0 are
+ *   skipped.  The rounding error of the risk is at most (levels x in-degree) 2^-41.
+ *   max_words: 1 .. ASR_LATTICE_MBR_MAX_WORDS, the words a hypothesis may hold in this launch.
+ *   out_num_words [B] i32; out_words, out_frames [B, max_words] i32, out_confidence [B, max_words] f64
+ *   (utterance b's at b max_words); out_risk [B] f64 (+inf and 0 words, 0 iterations: no nodes, no start
+ *   node, no complete path, or a NaN among the best path's costs); out_iterations [B] i32;
+ *   out_status [B] i32 bits: 1 an index out of range or a level that does not rise, 2 the sausage
+ *   buffer overflowed, 4 the hypothesis (given, the best path's, or after an update) holds more than
+ *   max_words words; with 2 or 4 the caller redoes the utterance on the host.
+ *   The sausage: out_sausage_key, _gamma, _tau [B, sausage_cap] i64, an open-addressing table the kernel
+ *   accumulates in: key = slot << 32 | word (-1: empty), gamma at 2^-52, tau as above; the entries of the
+ *   last evaluation with key >= 0 and gamma > 0 are the confusion network, out_sausage_count [B] their
+ *   number, in no particular order.
+ *   workspace: asr_lattice_mbr_workspace_bytes(nodes of the launch, max_words) = 16 (2 max_words + 2) + 8
+ *   bytes per node, rounded (alpha', beta', fwd; a is recomputed in the backward pass, so there is no
+ *   per-arc chain).  One workgroup per utterance and one launch for all iterations; a wave owns a node
+ *   of a level and takes its in-arcs in turn, its lanes run over the slots; A3 is a min-plus prefix scan
+ *   over the lanes and b a segmented suffix sum, both exact in integers, with a carry between 64-slot
+ *   rounds; beta', gamma and tau are summed with 64-bit integer atomics; workgroup barriers only.
+ */
+#define ASR_LATTICE_MBR_MAX_WORDS 255
+int asr_lattice_mbr_supported(int64_t N, int64_t A, int64_t L, int max_words);
+int64_t asr_lattice_mbr_workspace_bytes(int64_t num_nodes, int max_words);
+int asr_lattice_mbr_f64(
+    int B, int b_begin, int b_count, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
+    const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
+    const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
+    const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
+    double acoustic_scale, double lm_scale, int64_t num_states, int64_t num_graph_arcs, const float *arc_weight,
+    const int32_t *arc_olabel, const float *final_cost, int start, int threads, const double *arc_cond,
+    const double *end_cond, const int32_t *init_words, const int32_t *init_num_words, int max_iterations,
+    int max_words, int64_t sausage_cap, int32_t *out_num_words, int32_t *out_words, double *out_confidence,
+    int32_t *out_frames, double *out_risk, int32_t *out_iterations, int32_t *out_status,
+    int32_t *out_sausage_count, int64_t *out_sausage_key, int64_t *out_sausage_gamma, int64_t *out_sausage_tau,
+    void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

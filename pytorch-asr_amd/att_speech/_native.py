@@ -98,6 +98,11 @@ _SIGNATURES = {
     'asr_lattice_nbest_workspace_bytes': (_i64, [_i64, _i]),
     'asr_lattice_nbest_f64': (_i, [_i, _i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
                               [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 6 + [_i64, _vp]),
+    'asr_lattice_mbr_supported': (_i, [_i64, _i64, _i64, _i]),
+    'asr_lattice_mbr_workspace_bytes': (_i64, [_i64, _i]),
+    'asr_lattice_mbr_f64': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
+                            [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 4 + [_i, _i, _i64] + [_vp] * 11 +
+                            [_vp, _i64, _vp]),
     'asr_split_bf16_f32': (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     'asr_log_softmax_shift_bwd_split_blocks': (_i, [_i64]),
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),

@@ -6,7 +6,10 @@ same launch, the same canonical sort on the device, and a `DeviceLatticeBatch` i
 launch (`best_paths`: the recipe's acoustic-scale sweep, egs/wsj/ctc_kaldi_decode.sh:160-163, as one
 search plus one sweep) and computes arc, node, frame and word posteriors (`posteriors`:
 lattice-to-post).  DESIGN.md section 4.21.  `nbest` / `sentences` list its n cheapest distinct word
-sequences, the hand-over to AttentionDecoderTCN.score_sentences, in one launch (section 4.22).
+sequences, the hand-over to AttentionDecoderTCN.score_sentences, in one launch (section 4.22).  `mbr`
+decodes it by minimum Bayes risk (the word sequence of the least expected word edit distance, with
+per-word confidences and the confusion network) and `expected_errors` scores given sentences by that
+distance, all iterations in one launch of asr_lattice_mbr_f64 (section 4.23).
 
 A batch on a GPU runs asr_lattice_bestpath_f64 / asr_lattice_posterior_f64 / asr_lattice_nbest_f64
 (csrc/lattice_dp.hip); a batch of CPU tensors, or ASR_LATTICE_DP_NATIVE=0 (ASR_LATTICE_NBEST_NATIVE=0
@@ -22,11 +25,14 @@ import torch
 
 from att_speech import _native
 from att_speech.wfst_decode import DEFAULT_WORKSPACE_BYTES
-from att_speech.wfst_lattice import (INF, OVERFLOW_NAMES, Lattice, LatticeBatch, LatticePosteriors, _decode_device,
-                                     _order, _validate, decode_lattice_host, nbest_lists)
+from att_speech.wfst_lattice import (INF, MBR_NONE, OVERFLOW_NAMES, Lattice, LatticeBatch, LatticePosteriors,
+                                     MBRResult, _decode_device, _order, _validate, decode_lattice_host, mbr_sausage,
+                                     nbest_lists)
 
-THREADS_PER_WORKGROUP = 0       # 0: the kernels' default (64; nbest: 256); 64 / 128 / 256 for timing runs
+THREADS_PER_WORKGROUP = 0       # 0: the kernels' default (64; nbest and mbr: 256); 64 / 128 / 256 for timing runs
 NBEST_DEVICE_MAX = 64           # ASR_LATTICE_NBEST_MAX of include/asr_amd.h: a list entry per lane of a wave
+MBR_DEVICE_MAX_WORDS = 255      # ASR_LATTICE_MBR_MAX_WORDS: the longest hypothesis asr_lattice_mbr_f64 has columns for
+MBR_SAUSAGE_ENTRIES = 0         # sausage entries an utterance in mbr's buffer; 0: per slot a word of the graph each, at most 64
 
 
 def _h(a):
@@ -366,6 +372,144 @@ class DeviceLatticeBatch(object):
     def sentences(self, n, **kw):
         """the word lists of nbest(n) per utterance: what AttentionDecoderTCN.score_sentences takes"""
         return [[w for w, _ in row] for row in self.nbest(n, **kw)]
+
+    # ---- minimum-Bayes-risk decoding -------------------------------------------------------------
+    def mbr(self, acoustic_scale=None, lm_scale=1.0, max_iterations=16, hypotheses=None, workspace_bytes=None,
+            arc_cond=None, end_cond=None, max_words=None):
+        """Minimum-Bayes-risk decoding of every lattice: one MBRResult per utterance (words, confidence,
+        frames, risk, iterations, sausage); the semantics are LatticeBatch.mbr's (DESIGN.md section
+        4.23, include/asr_amd.h): the word sequence of the least expected word edit distance under the
+        lattice's path distribution at these scales, from `hypotheses` (a word list per utterance) or
+        the best path, by at most max(1, max_iterations) edit-distance forward-backward passes.
+
+        On a GPU all utterances and all iterations are one launch of asr_lattice_mbr_f64, or several
+        when workspace_bytes (default: the batch's) does not hold 16 (2 max_words + 2) + 8 bytes per
+        node at once; self.launches counts them.  max_words (default: the most levels of an utterance,
+        at most MBR_DEVICE_MAX_WORDS) is the longest hypothesis the launch has columns for.
+        arc_cond / end_cond (fp64, per arc / node, numpy or tensors): LatticeBatch.conditionals'
+        values instead of the kernel's own forward pass; with them the result equals the twin's with ==.
+        A batch of CPU tensors and ASR_LATTICE_MBR_NATIVE=0 (read per call) run LatticeBatch.mbr on a
+        copy; so do, with one warning per call, the utterances whose hypothesis outgrew max_words or
+        whose sausage outgrew its buffer."""
+        B = self.num_utterances
+        if hypotheses is not None:
+            if len(hypotheses) != B:
+                raise ValueError("hypotheses must hold one word list per utterance")
+            hypotheses = [[int(w) for w in h] for h in hypotheses]
+            if any(w <= 0 for h in hypotheses for w in h):
+                raise ValueError("hypotheses hold word labels > 0")
+
+        def host(x):
+            return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
+        self.launches = 0
+        native = self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_MBR_NATIVE', '1') != '0'
+        if not native:
+            return self._host_batch().mbr(acoustic_scale, lm_scale, max_iterations, hypotheses, host(arc_cond),
+                                          host(end_cond))
+        if B == 0 or self.num_nodes == 0:
+            return [MBR_NONE] * B
+        L = _native.lib()
+        levels = np.diff(self.level_off)
+        W = int(levels.max()) if max_words is None else int(max_words)
+        W = max(1, min(W, MBR_DEVICE_MAX_WORDS))
+        if not L.asr_lattice_mbr_supported(self.num_nodes, self.num_arcs, self.num_levels, W):
+            raise NotImplementedError("asr_lattice_mbr_f64: the batch is too large")
+        if getattr(self, '_mbr_labels', None) is None:     # the graph's distinct words, and 0: no slot holds more
+            ol = np.asarray(self.graph.olabel)
+            self._mbr_labels = int(len(np.unique(ol[ol != 0]))) + 1
+        cap = int(MBR_SAUSAGE_ENTRIES) or min(self._mbr_labels, 64) * (2 * W + 2)
+        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
+        dev, p = self.device, _native._p
+        chunks = self._utterance_chunks(16 * (2 * W + 2) + 8, budget - 64)
+        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
+        nbytes = L.asr_lattice_mbr_workspace_bytes(biggest, W)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+
+        def cond(x, n, what):
+            if x is None:
+                return None
+            x = torch.as_tensor(x).to(dev, torch.float64).contiguous()
+            if x.numel() != n:
+                raise ValueError("%s must have %d entries" % (what, n))
+            return x
+        arc_cond, end_cond = cond(arc_cond, self.num_arcs, 'arc_cond'), cond(end_cond, self.num_nodes, 'end_cond')
+        init_w = init_n = None
+        if hypotheses is not None:
+            rows = np.zeros((B, W), np.int32)
+            counts = np.zeros(B, np.int32)
+            for b, h in enumerate(hypotheses):
+                counts[b] = len(h) if len(h) <= W else -1      # -1: the kernel hands the utterance back
+                if len(h) <= W:
+                    rows[b, :len(h)] = h
+            init_w, init_n = torch.from_numpy(rows).to(dev), torch.from_numpy(counts).to(dev)
+        small = torch.zeros((4, B), **i32)              # words, iterations, status, sausage entries
+        words, frames = torch.zeros((B, W), **i32), torch.zeros((B, W), **i32)
+        conf, risk = torch.zeros((B, W), **f64), torch.full((B,), INF, **f64)
+        table = torch.full((3, B, cap), -1, dtype=torch.int64, device=dev)
+        head, tail = self._common_args()
+        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
+        for b0, b1 in chunks:
+            self._check(L.asr_lattice_mbr_f64(
+                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(arc_cond), p(end_cond), p(init_w), p(init_n),
+                int(max_iterations), W, cap, p(small[0]), p(words), p(conf), p(frames), p(risk), p(small[1]),
+                p(small[2]), p(small[3]), p(table[0]), p(table[1]), p(table[2]), p(ws), nbytes,
+                _native._stream()), 'asr_lattice_mbr_f64')
+            self.launches += 1
+        nw_h, it_h, status_h, _ = small.cpu().numpy()
+        if (status_h & 1).any():
+            raise ValueError("asr_lattice_mbr_f64: the batch's index arrays are inconsistent")
+        used = torch.nonzero(((table[0] >= 0) & (table[1] > 0)).reshape(-1)).reshape(-1)    # the entries alone cross
+        t_utt = torch.div(used, cap, rounding_mode='floor').cpu().numpy()
+        t_key, t_gamma, t_tau = (table[j].reshape(-1)[used].cpu().numpy() for j in range(3))
+        tables = [{} for _ in range(B)]
+        for b, k, g, t in zip(t_utt.tolist(), t_key.tolist(), t_gamma.tolist(), t_tau.tolist()):
+            tables[b][(k >> 32, k & 0xFFFFFFFF)] = (g, t)
+        words_h, frames_h, conf_h, risk_h = words.cpu().numpy(), frames.cpu().numpy(), conf.cpu().numpy(), \
+            risk.cpu().numpy()
+        out = []
+        for b in range(B):
+            if status_h[b] or not risk_h[b] < INF:
+                out.append(MBR_NONE)
+                continue
+            n = int(nw_h[b])
+            out.append(MBRResult(words_h[b, :n].tolist(), conf_h[b, :n].tolist(), frames_h[b, :n].tolist(),
+                                 float(risk_h[b]), int(it_h[b]), mbr_sausage(tables[b])))
+        redo = np.nonzero(status_h)[0].tolist()
+        if redo:
+            warnings.warn("mbr: %d of %d utterances outgrew the device's %d words a hypothesis or %d sausage "
+                          "entries and were redone on the host" % (len(redo), B, W, cap))
+            lats = self._host_batch().lattices
+            ac, ec = host(arc_cond), host(end_cond)
+            pick = np.concatenate
+            sub = LatticeBatch([lats[b] for b in redo]).mbr(
+                acoustic_scale, lm_scale, max_iterations,
+                None if hypotheses is None else [hypotheses[b] for b in redo],
+                None if ac is None else pick([ac[self.arc_off[b]:self.arc_off[b + 1]] for b in redo]),
+                None if ec is None else pick([ec[self.node_off[b]:self.node_off[b + 1]] for b in redo]))
+            for b, r in zip(redo, sub):
+                out[b] = r
+        return out
+
+    def expected_errors(self, sentences, acoustic_scale=None, lm_scale=1.0, **kw):
+        """The expected word edit distance of given sentences over their lattices: `sentences` holds a
+        list of word lists per utterance (the shape sentences(n) returns); returns the risks in that
+        shape (+inf: no lattice).  mbr(max_iterations=0, hypotheses=...) once per list position, so n
+        sentences an utterance are n launches (self.launches counts them all), each with its own
+        forward pass, table and read-back: the hand-over that lets a rescoring stage weigh a candidate by its expected word error."""
+        if len(sentences) != self.num_utterances:
+            raise ValueError("sentences must hold one list per utterance")
+        out = [[] for _ in sentences]
+        launches = 0
+        for i in range(max([len(s) for s in sentences] + [0])):
+            res = self.mbr(acoustic_scale, lm_scale, 0, [s[i] if i < len(s) else [] for s in sentences], **kw)
+            launches += self.launches
+            for b, s in enumerate(sentences):
+                if i < len(s):
+                    out[b].append(res[b].risk)
+        self.launches = launches
+        return out
 
     # ---- the log-semiring pass ----------------------------------------------------------------
     def posteriors(self, acoustic_scale=None, lm_scale=1.0, workspace_bytes=None):

@@ -604,7 +604,7 @@ class FSTDecoder(_ProjectionDecoder):
                  numerator_red='logsumexp', denominator_red='logsumexp',
                  embedder='LutLinear', embedder_kwargs={}, decode_beam=None,
                  decode_lattice_beam=None, decode_nbest=1, decode_confidence=False,
-                 decode_nbest_device=False, **kwargs):
+                 decode_nbest_device=False, decode_mbr=False, **kwargs):
         super(FSTDecoder, self).__init__(**kwargs)
         # decode_beam: None = the exact every-state Viterbi below; a number = the beam-pruned
         # token-passing search (att_speech/wfst_decode.py) over the same graph with that beam
@@ -617,10 +617,16 @@ class FSTDecoder(_ProjectionDecoder):
         # decode_nbest_device: 'nbest' comes from the lattices where the search left them
         # (DeviceLatticeBatch.nbest, one launch per batch) instead of Lattice.nbest per utterance
         # on the host: the same costs; sequences that tie at the last place may differ
+        # decode_mbr: decode() also adds 'mbr': per utterance (labels, confidence, frames) of the
+        # minimum-Bayes-risk label sequence at the search scale (DeviceLatticeBatch.mbr, one launch
+        # per batch), and 'mbr_risk': its expected label edit distance under the lattice
         if decode_lattice_beam is not None and decode_beam is None:
             raise ValueError("decode_lattice_beam needs decode_beam: the lattice comes from the beam search")
         if decode_confidence and decode_lattice_beam is None:
             raise ValueError("decode_confidence needs decode_lattice_beam: the posteriors are the lattice's")
+        if decode_mbr and decode_lattice_beam is None:
+            raise ValueError("decode_mbr needs decode_lattice_beam: the risk is taken over the lattice")
+        self.decode_mbr = bool(decode_mbr)
         self.decode_beam, self.decode_confidence = decode_beam, bool(decode_confidence)
         self.decode_lattice_beam, self.decode_nbest = decode_lattice_beam, int(decode_nbest)
         self.decode_nbest_device = bool(decode_nbest_device)
@@ -731,7 +737,8 @@ class FSTDecoder(_ProjectionDecoder):
             res = wfst_decode.decode_graph(logits.detach().float(), encoded_lens, self._decoding_graph,
                                            beam=float(self.decode_beam))
             ret = {'decoded': res['words'], 'logits': logits}   # the labels on the winning arcs
-            if self.decode_lattice_beam is not None and (self.decode_confidence or self.decode_nbest_device):
+            if self.decode_lattice_beam is not None and (self.decode_confidence or self.decode_nbest_device
+                                                         or getattr(self, 'decode_mbr', False)):
                 from att_speech import lattice_dp
                 batch, _ = lattice_dp.decode_lattice_device(
                     logits.detach().float(), encoded_lens, self._decoding_graph, beam=float(self.decode_beam),
@@ -743,6 +750,10 @@ class FSTDecoder(_ProjectionDecoder):
                 if self.decode_confidence:
                     ret['word_confidence'] = [[p for _, _, p in row]
                                               for row in batch.posteriors().word_posteriors(window=0)]
+                if getattr(self, 'decode_mbr', False):
+                    mbr = batch.mbr()
+                    ret['mbr'] = [(r.words, r.confidence, r.frames) for r in mbr]
+                    ret['mbr_risk'] = [r.risk for r in mbr]
             elif self.decode_lattice_beam is not None:
                 from att_speech import wfst_lattice
                 lats, _ = wfst_lattice.decode_lattice(

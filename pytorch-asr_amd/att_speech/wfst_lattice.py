@@ -20,6 +20,7 @@ that survive the prune (S_n = V_n), thr_k the threshold of frame k's emitting ph
   kept           alpha(u) + (x + beta(v)) <= best + lattice_beam (and finite), plus the arcs of
                  the search's own traceback
 """
+import collections
 import heapq
 import os
 import warnings
@@ -111,6 +112,11 @@ class Lattice(object):
         """LatticeBatch.posteriors of this lattice alone"""
         return LatticeBatch([self]).posteriors(acoustic_scale, lm_scale)
 
+    def mbr(self, acoustic_scale=None, lm_scale=1.0, max_iterations=16, hypothesis=None, **kw):
+        """LatticeBatch.mbr of this lattice alone: one MBRResult"""
+        hyps = None if hypothesis is None else [hypothesis]
+        return LatticeBatch([self]).mbr(acoustic_scale, lm_scale, max_iterations, hyps, **kw)[0]
+
     def nbest(self, n, acoustic_scale=None, lm_scale=1.0, max_expansions=DEFAULT_MAX_EXPANSIONS):
         """The n cheapest DISTINCT word sequences as [(words, cost)], sorted by (cost, words).
 
@@ -177,6 +183,58 @@ class Lattice(object):
 
 
 NBEST_HASH_MUL = 0x9E3779B97F4A7C15     # H(o, h) = h * NBEST_HASH_MUL + o + 1 mod 2^64: LatticeBatch.nbest
+
+
+# minimum-Bayes-risk decoding (LatticeBatch.mbr, asr_lattice_mbr_f64): the
+# expected distances are int64 at 2^-40, the masses int64 at 2^-52, Kaldi's delta = 1e-5 is 10995116
+MBR_ONE = 1 << 40
+MBR_DELTA = 10995116
+MBR_SUB = MBR_ONE + MBR_DELTA           # a substitution, and a lattice word matched to nothing
+MBR_MASS = 1 << 52
+MBR_TAU_SHIFT = 12
+
+MBRResult = collections.namedtuple('MBRResult', 'words confidence frames risk iterations sausage')
+MBRResult.__doc__ = """One utterance's minimum-Bayes-risk result: words, per word its confidence (the mass gamma
+of its slot that agrees with it) and frame (the mass-weighted mean end time), risk (the expected word
+edit distance of `words` under the lattice's path distribution; +inf: no lattice), iterations (the
+number of evaluations) and sausage: per slot that holds a word or an alternative to a gap,
+[(word, gamma)] sorted by (-gamma, word), word 0 standing for no word."""
+
+MBR_NONE = MBRResult([], [], [], INF, 0, [])
+
+
+def _mbr_frame(tau, gamma):
+    """the frame of a word: tau = sum of (mass >> 12) * time over gamma's mass, to the nearest integer"""
+    g = int(gamma) >> MBR_TAU_SHIFT
+    return int(np.rint(float(int(tau)) / float(g))) if g > 0 else 0
+
+
+def mbr_sausage(table):
+    """the confusion network of {(slot, word): (gamma, tau)} (integers): per slot [(word, gamma)] by
+    (-gamma, word); a gap slot whose only entry is word 0 is left out"""
+    slots = {}
+    for (q, w), (g, _) in table.items():
+        if g > 0:
+            slots.setdefault(q, []).append((int(w), float(int(g)) / MBR_MASS))
+    sausage = []
+    for q in sorted(slots):
+        row = sorted(slots[q], key=lambda e: (-e[1], e[0]))
+        if q % 2 == 1 and len(row) == 1 and row[0][0] == 0:
+            continue
+        sausage.append(row)
+    return sausage
+
+
+def mbr_result(words, risk, iterations, table):
+    """an MBRResult from the words, the risk as int64 at 2^-40, and {(slot, word): (gamma, tau)} in
+    integers"""
+    conf, frames = [], []
+    for k, w in enumerate(words):
+        g, t = table.get((2 * k + 2, w), (0, 0))
+        conf.append(float(int(g)) / MBR_MASS)
+        frames.append(_mbr_frame(t, g))
+    return MBRResult([int(w) for w in words], conf, frames, float(int(risk)) / MBR_ONE, int(iterations),
+                     mbr_sausage(table))
 
 
 class _Entries(object):
@@ -461,6 +519,220 @@ class LatticeBatch(object):
                            part + bwd[self.dst] - za, -INF)
         return LatticePosteriors(self, log_z, arc, node, acoustic_scale, lm_scale)
 
+    # ---- minimum-Bayes-risk decoding ---------------------------------------------------------
+    def conditionals(self, acoustic_scale=None, lm_scale=1.0):
+        """(arc_cond [arcs], end_cond [nodes]) in linear fp64: the probability of in-arc j given that a
+        path passes through its destination, exp((fwd(src) - x) - fwd(dst)), and of stopping at node v
+        given a complete path, exp((fwd(v) - fl(lm end(v))) - log_z); fwd as in posteriors.  0 where
+        a term is infinite."""
+        B = len(self.lattices)
+        N = len(self.time) if B else 0
+        if not N:
+            return np.zeros(0), np.zeros(0)
+        sc = self.scale if acoustic_scale is None else float(acoustic_scale)
+        lm = float(lm_scale)
+        x = lm * self.w - sc * self.lp
+        fwd = np.where(self.start, 0.0, -INF)
+        with np.errstate(invalid='ignore', over='ignore'):
+            for lv, src, _, _ in self.levels:
+                ok = fwd[src] > -INF
+                np.logaddexp.at(fwd, self.dst[lv][ok], fwd[src][ok] - x[lv][ok])
+            is_end = (self.end < INF) & (fwd > -INF)
+            stop = np.where(is_end, fwd - lm * np.where(self.end < INF, self.end, 0.0), -INF)
+            log_z = np.full(B, -INF)
+            np.logaddexp.at(log_z, self.n_utt[is_end], stop[is_end])
+            end_cond = np.where(stop > -INF, np.exp(stop - log_z[self.n_utt]), 0.0)
+            ok = (fwd[self.src] > -INF) & (x < INF) & (fwd[self.dst] > -INF)
+            arc_cond = np.where(ok, np.exp((fwd[self.src] - x) - fwd[self.dst]), 0.0)
+        return np.where(arc_cond > 0, arc_cond, 0.0), np.where(end_cond > 0, end_cond, 0.0)
+
+    def mbr(self, acoustic_scale=None, lm_scale=1.0, max_iterations=16, hypotheses=None, arc_cond=None,
+            end_cond=None):
+        """Minimum-Bayes-risk decoding (Xu, Povey, Mangu, Zhu 2011; Kaldi's lattice-mbr-decode): per
+        utterance the word sequence that minimises the expected word edit distance under the lattice's
+        path distribution at these scales, with per-word confidences, frames and the confusion network.
+        One MBRResult per utterance.  The numpy twin of asr_lattice_mbr_f64 (include/asr_amd.h states
+        the semantics), in the same integer arithmetic, so both give the same results with ==.
+
+        Start: `hypotheses` (a word list per utterance) or the best path's words.  Every evaluation is
+        an edit-distance forward-backward over (node, hypothesis slot); then every slot takes the
+        word of the largest mass gamma (ties: the current word, else the smallest label).  It stops
+        when the words did not change or after max(1, max_iterations) evaluations; the result is the
+        last evaluated hypothesis's, so max_iterations=0 with hypotheses scores them unchanged.
+        arc_cond / end_cond override conditionals().  No lattice or no complete path: MBR_NONE."""
+        B = len(self.lattices)
+        N = len(self.time) if B else 0
+        if hypotheses is not None and len(hypotheses) != B:
+            raise ValueError("hypotheses must hold one word list per utterance")
+        if not N:
+            return [MBR_NONE] * B
+        if arc_cond is None or end_cond is None:
+            ac, ec = self.conditionals(acoustic_scale, lm_scale)
+            arc_cond = ac if arc_cond is None else arc_cond
+            end_cond = ec if end_cond is None else end_cond
+        pi, pe = np.asarray(arc_cond, np.float64), np.asarray(end_cond, np.float64)
+        if len(pi) != len(self.arc) or len(pe) != N:
+            raise ValueError("arc_cond / end_cond must have one entry per arc / node")
+        pi, pe = np.where(pi > 0, pi, 0.0), np.where(pe > 0, pe, 0.0)
+        first = np.full(B, N, np.int64)
+        np.minimum.at(first, self.n_utt[self.start], np.nonzero(self.start)[0])
+        live = first < N
+        ends = np.zeros(B, bool)
+        ends[self.n_utt[pe > 0]] = True
+        live &= ends
+        if hypotheses is None:
+            with np.errstate(invalid='ignore'):
+                best = self.best_paths(acoustic_scale, lm_scale)
+            hyps = [list(w) for w, _, _, _ in best]
+            live &= np.array([c < INF for _, c, _, _ in best])
+        else:
+            hyps = [[int(w) for w in h] for h in hypotheses]
+            if any(w <= 0 for h in hyps for w in h):
+                raise ValueError("hypotheses hold word labels > 0")
+        n_max = max(1, int(max_iterations))
+        results = [MBR_NONE] * B
+        iters = np.zeros(B, np.int64)
+        while live.any():
+            risk, tables = self._mbr_evaluate(hyps, live, pi, pe, first)
+            for b in np.nonzero(live)[0].tolist():
+                iters[b] += 1
+                new = hyps[b]
+                if iters[b] < n_max:
+                    new = mbr_update(hyps[b], tables[b])
+                if new == hyps[b]:
+                    results[b] = mbr_result(hyps[b], risk[b], iters[b], tables[b])
+                    live[b] = False
+                hyps[b] = new
+        return results
+
+    def _mbr_evaluate(self, hyps, live, pi, pe, first):
+        """one edit-distance forward-backward of the live utterances: (risk [B] int64 at 2^-40, per
+        utterance {(slot, word): (gamma, tau)})"""
+        B, N = len(self.lattices), len(self.time)
+        i64 = np.int64
+        S = np.array([2 * len(h) + 1 if live[b] else 0 for b, h in enumerate(hyps)], i64)
+        C = int(S.max()) + 1
+        col = np.arange(C)
+        R = np.zeros((B, C), i64)
+        for b in np.nonzero(live)[0]:
+            R[b, 2:S[b]:2] = hyps[b]
+        dl = np.where(R != 0, MBR_ONE, 0).astype(i64)
+        Dc = np.cumsum(dl, axis=1)
+        valid = col[None, :] <= S[:, None]
+        a_utt = self.n_utt[self.src]
+        starts = first[live]
+        is_start = np.zeros(N, bool)
+        is_start[starts] = True
+        alpha = np.zeros((N, C), i64)
+        alpha[starts] = Dc[live]
+
+        def chain(au, w, utt):
+            ins = np.where(w != 0, MBR_SUB, 0).astype(i64)[:, None]
+            sub = np.where(w[:, None] == R[utt], 0, MBR_SUB).astype(i64)
+            A2 = au + ins
+            A1 = np.full_like(au, 1 << 60)
+            A1[:, 1:] = au[:, :-1] + sub[:, 1:]
+            d = Dc[utt]
+            return A1, A2, d + np.minimum.accumulate(np.minimum(A1, A2) - d, axis=1)
+
+        def weigh(p, v, utt):
+            out = np.rint(p[:, None] * v.astype(np.float64)).astype(i64)
+            out[~valid[utt]] = 0
+            return out
+
+        groups = []
+        for lv, src, _, _ in self.levels:
+            keep = live[a_utt[lv]] & ~is_start[self.dst[lv]] & (pi[lv] > 0)
+            if keep.any():
+                groups.append((lv[keep], src[keep], a_utt[lv[keep]]))
+        for lv, src, utt in groups:
+            a = chain(alpha[src], self.ol[lv], utt)[2]
+            np.add.at(alpha, self.dst[lv], weigh(pi[lv], a, utt))
+        ev = np.nonzero((pe > 0) & live[self.n_utt])[0]
+        e_utt = self.n_utt[ev]
+        no_word = np.zeros(len(ev), i64)
+        alpha_e = np.zeros((B, C), i64)
+        np.add.at(alpha_e, e_utt, weigh(pe[ev], chain(alpha[ev], no_word, e_utt)[2], e_utt))
+        risk = alpha_e[np.arange(B), S]
+
+        beta = np.zeros((N, C), i64)
+        flat = beta.reshape(-1)
+        beta_e = np.zeros((B, C), i64)
+        beta_e[live, S[live]] = MBR_MASS
+        k_utt, k_q, k_w, k_g, k_t = [], [], [], [], []
+
+        def note(utt, q, w, g, t):
+            k_utt.append(utt), k_q.append(q), k_w.append(w), k_g.append(g), k_t.append(t)
+
+        def back(u, w, utt, p, bv, tv):
+            A1, A2, a = chain(alpha[u], w, utt)
+            A3 = np.zeros_like(a)
+            A3[:, 1:] = a[:, :-1] + dl[utt][:, 1:]
+            c1 = (A1 <= A2) & (A1 <= A3)
+            c2 = ~c1 & (A2 <= A3)
+            c3 = ~c1 & ~c2
+            c1[:, 0] = c2[:, 0] = c3[:, 0] = False
+            mass = weigh(p, bv, utt)
+            n = len(mass)
+            # b(q) = mass(q) + (case 3 at q + 1 ? b(q + 1) : 0): suffix sums cut where the chain breaks
+            cs = np.zeros((n, C + 1), i64)
+            cs[:, :C] = np.cumsum(mass[:, ::-1], axis=1)[:, ::-1]
+            brk = np.concatenate([np.where(c3, C, col[None, :]), np.full((n, 1), C)], axis=1)
+            nxt = np.minimum.accumulate(brk[:, ::-1], axis=1)[:, ::-1][:, 1:]
+            b = cs[:, :C] - np.take_along_axis(cs, nxt, axis=1)
+            rows, cols = np.nonzero(b > 0)
+            bb = b[rows, cols]
+            k1, k2, k3, k0 = c1[rows, cols], c2[rows, cols], c3[rows, cols], cols == 0
+            np.add.at(flat, u[rows[k1]] * C + cols[k1] - 1, bb[k1])
+            np.add.at(flat, u[rows[k2]] * C + cols[k2], bb[k2])
+            np.add.at(flat, u[rows[k0]] * C, bb[k0])
+            note(utt[rows[k1]], cols[k1], w[rows[k1]], bb[k1], (bb[k1] >> MBR_TAU_SHIFT) * tv[rows[k1]])
+            note(utt[rows[k3]], cols[k3], np.zeros(int(k3.sum()), i64), bb[k3], np.zeros(int(k3.sum()), i64))
+
+        frames = np.array([l.num_frames for l in self.lattices], i64)
+        back(ev, no_word, e_utt, pe[ev], beta_e[e_utt], frames[e_utt])
+        for lv, src, utt in reversed(groups):
+            back(src, self.ol[lv].astype(i64), utt, pi[lv], beta[self.dst[lv]], self.time[self.dst[lv]])
+        # the start node: nothing of the lattice is left, the rest of the hypothesis is deleted
+        tail = np.where(valid[live], beta[starts], 0)
+        tail = np.cumsum(tail[:, ::-1], axis=1)[:, ::-1]
+        tail[:, 0] = 0
+        rows, cols = np.nonzero(tail > 0)
+        note(np.nonzero(live)[0][rows], cols, np.zeros(len(rows), i64), tail[rows, cols], np.zeros(len(rows), i64))
+        utt, q, w, g, t = (np.concatenate(x).astype(i64) for x in (k_utt, k_q, k_w, k_g, k_t))
+        V = int(max(self.ol.max() if len(self.ol) else 0, 0)) + 1
+        key, inv = np.unique((utt * C + q) * V + w, return_inverse=True)
+        gs, ts = np.zeros(len(key), i64), np.zeros(len(key), i64)
+        np.add.at(gs, inv, g)
+        np.add.at(ts, inv, t)
+        tables = [{} for _ in range(B)]
+        for k, gi, ti in zip(key.tolist(), gs.tolist(), ts.tolist()):
+            slot, word = divmod(k, V)
+            b, qq = divmod(slot, C)
+            tables[b][(qq, word)] = (gi, ti)
+        return risk, tables
+
+
+def mbr_update(words, table):
+    """the next hypothesis: every slot takes the word of the largest gamma; among equal maxima the
+    slot's current word if it is one of them, else the smallest label; the zeros are dropped"""
+    S = 2 * len(words) + 1
+    slots = [[] for _ in range(S + 1)]
+    for (q, w), (g, _) in table.items():
+        if g > 0 and 1 <= q <= S:
+            slots[q].append((g, w))
+    new = []
+    for q in range(1, S + 1):
+        if not slots[q]:
+            continue
+        top = max(g for g, _ in slots[q])
+        cands = [w for g, w in slots[q] if g == top]
+        cur = words[q // 2 - 1] if q % 2 == 0 else 0
+        w = cur if cur in cands else min(cands)
+        if w != 0:
+            new.append(int(w))
+    return new
+
 
 class LatticePosteriors(object):
     """What LatticeBatch.posteriors and DeviceLatticeBatch.posteriors return.
@@ -520,8 +792,9 @@ class LatticePosteriors(object):
         the best path at these scales: the summed posterior of the utterance's arcs that carry the
         same word and end within `window` frames of that arc's end time, clipped to 1.  Computed
         on the host.  This is a time-window confidence (how much of the lattice's probability mass
-        agrees that the word is spoken there), not Kaldi's MBR confidence: no edit-distance
-        alignment between paths is made."""
+        agrees that the word is spoken there): no edit-distance alignment between paths is made.
+        The edit-distance-aligned confidence, Kaldi's MBR confidence, is `mbr(...)`'s: MBRResult's
+        `confidence`, the mass gamma of a word's slot (LatticeBatch.mbr, DeviceLatticeBatch.mbr)."""
         hb = self._host_batch()
         _, word_arcs = hb._best_paths(self.acoustic_scale, self.lm_scale)
         post = self.arc_log_post

@@ -4,7 +4,7 @@ reference's scoring recipe (egs/wsj/ctc_kaldi_decode.sh:141-147) without Kaldi.
 
     python tools/decode_graph.py LOGPROBS.ark GRAPH.fst [--words words.txt] [--beam 16]
         [--acoustic-scale 1.0] [--batch 64] [--device cuda:0|cpu] [--out FILE]
-        [--lattice-beam X --nbest N [--device-nbest] [--acwt-sweep LO:HI:STEP] [--post OUT.npz]]
+        [--lattice-beam X --nbest N [--device-nbest] [--acwt-sweep LO:HI:STEP] [--post OUT.npz] [--mbr OUT]]
 
 LOGPROBS.ark: the float-matrix archive att_speech.ctc_forward writes (one [frames, classes] matrix
 per utterance).  GRAPH.fst: an OpenFst binary (vector/standard, plain or gzip) or an AT&T text
@@ -21,7 +21,10 @@ LO, LO + STEP, ..., HI, which the recipe does with one decode-faster run per sca
 (egs/wsj/ctc_kaldi_decode.sh:160-163): lines `scale uttid cost w1 w2 ...`, scale by scale.  The
 lattices stay on the device and all scales are one call (att_speech.lattice_dp).  With --post the
 frame-level class posteriors of every lattice (lattice-to-post) go to OUT.npz, one
-[frames, classes] float32 matrix per utterance key, and nothing else is written."""
+[frames, classes] float32 matrix per utterance key, and nothing else is written.  With --mbr OUT
+every lattice is decoded by minimum Bayes risk (DeviceLatticeBatch.mbr: lattice-mbr-decode, one launch
+per batch): `uttid w1 w2 ...` lines go to OUT and `uttid word frame confidence` rows to OUT.conf, and
+nothing else is written."""
 import argparse
 import os
 import sys
@@ -130,6 +133,23 @@ def write_post(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_
     np.savez(path, **mats)
 
 
+def write_mbr(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_partial=True, device='cpu',
+              batch=64, table=None):
+    """OUT: `uttid w1 w2 ...`, the minimum-Bayes-risk word sequence of every lattice at the search's
+    scales; OUT.conf: `uttid word frame confidence`, a row per word"""
+    from att_speech.lattice_dp import decode_lattice_device
+    with open(path, 'w') as out, open(path + '.conf', 'w') as conf:
+        for keys, lp, lens in _batches(utts, batch):
+            every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, beam=beam,
+                                             lattice_beam=lattice_beam, acoustic_scale=acoustic_scale,
+                                             allow_partial=allow_partial)
+            for key, res in zip(keys, every.mbr()):
+                tokens = _tokens(table, res.words)
+                out.write(' '.join([key] + tokens) + '\n')
+                for tok, frame, c in zip(tokens, res.frames, res.confidence):
+                    conf.write('%s %s %d %.6f\n' % (key, tok, frame, c))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('logprobs')
@@ -147,9 +167,10 @@ def main(argv=None):
                     help='list the n-best on the device, a batch per launch (DeviceLatticeBatch.nbest)')
     ap.add_argument('--acwt-sweep', default=None, help='LO:HI:STEP: the 1-best per acoustic scale from one search')
     ap.add_argument('--post', default=None, help='OUT.npz: frame-level class posteriors of every lattice')
+    ap.add_argument('--mbr', default=None, help='OUT: minimum-Bayes-risk transcripts; OUT.conf: word confidences')
     a = ap.parse_args(argv)
-    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post or a.device_nbest):
-        ap.error('--nbest, --device-nbest, --acwt-sweep and --post need --lattice-beam')
+    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post or a.device_nbest or a.mbr):
+        ap.error('--nbest, --device-nbest, --acwt-sweep, --post and --mbr need --lattice-beam')
     from att_speech import wfst_decode
     from att_speech.ctc_forward import read_kaldi_float_matrices
     from att_speech.lm_fst import SymbolTable
@@ -162,7 +183,9 @@ def main(argv=None):
         utts = [(k, mats[k]) for k in keys]
         kw = dict(beam=a.beam, lattice_beam=a.lattice_beam, acoustic_scale=a.acoustic_scale,
                   allow_partial=not a.no_allow_partial, device=device, batch=a.batch, table=table)
-        if a.post:
+        if a.mbr:
+            write_mbr(graph, utts, a.mbr, **kw)
+        elif a.post:
             write_post(graph, utts, a.post, **kw)
         elif a.acwt_sweep:
             write_sweep(graph, utts, a.out, scales=parse_sweep(a.acwt_sweep), **kw)
