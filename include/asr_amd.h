@@ -1442,6 +1442,67 @@ int asr_lattice_mbr_f64(
     int32_t *out_sausage_count, int64_t *out_sausage_key, int64_t *out_sausage_gamma, int64_t *out_sausage_tau,
     void *workspace, int64_t workspace_bytes, void *stream);
 
+/*
+ * asr_lattice_lmrescore_*: lattice o back-off n-gram LM for a batch that stays on the device
+ * (csrc/lattice_lm.hip; att_speech/lattice_lm.py states the semantics and holds the
+ * numpy twin, which gives the same bits).  Three entries, called in this order for the utterances
+ * [b_begin, b_begin + b_count) of a batch in the layout of asr_lattice_bestpath_f64; src_global / dst_global
+ * [A] int64 are the arcs' end points as batch node indices, arc_utt [A] int64 their utterance.
+ *
+ * The LM in back-off form: lm_ptr [lm_states + 1], lm_label / lm_dst / lm_weight [lm_arcs] the non-epsilon
+ * arcs by (state, label), labels distinct within a state; lm_bo_dst [lm_states] (-1: none) and lm_bo_w the
+ * back-off arc; label_map [label_map_len] int64 takes an output label of the graph to a label of the LM
+ * (<= 0 or outside the map: out of vocabulary, the arc costs oov_cost and keeps the LM state; +inf drops it).
+ *
+ *   expand   per node the sorted distinct LM states that reach it, at most max_lm_states
+ *            (1 .. ASR_LATTICE_LMRESCORE_MAX_STATES) in the workspace; out_count [N] their number,
+ *            out_status [B]: bit 0 an utterance outgrew max_lm_states (its counts are then meaningless and
+ *            the caller zeroes them), bit 1 inconsistent index arrays.
+ *   emit     node_slot [nodes of the launch + 1] and arc_slot [arcs of the launch + 1] are the exclusive prefix
+ *            sums of count over the nodes and of count[source] over the arcs; E and M their totals.  Writes the LM
+ *            state of every expanded node and, per (arc, LM state of its source), the expanded end points
+ *            (launch-local), the source's LM state, the LM cost c (fp64, summed along the back-off chain in
+ *            order), weight = fl32(fl64(w) + scale * c), acoustic = -(fl32(own_scale) * lp), and out_ok: 1 kept,
+ *            0 dropped as out of vocabulary, -1 inconsistent.  Reads the workspace expand left.
+ *   sweep    over an expanded lattice in canonical order with its own level structure (all B utterances in one
+ *            launch): alpha, beta in fp32 with one rounding per operation, out_best [B] = min over the end
+ *            nodes of (alpha + end) + 0, and out_keep [M] (zero on entry): 1 where alpha(u) + (((w + a) +
+ *            beta(v)) + 0) is finite and <= best + lattice_beam (+inf: finite), or the arc lies on the forward
+ *            traceback from the first best end node.  No atomics: two runs give the same bits.
+ */
+#define ASR_LATTICE_LMRESCORE_MAX_STATES 1024
+int asr_lattice_lmrescore_supported(int64_t N, int64_t A, int64_t L, int max_lm_states);
+int64_t asr_lattice_lmrescore_workspace_bytes(int64_t num_nodes, int max_lm_states);
+int asr_lattice_lmrescore_expand(
+    int B, int b_begin, int b_count, int max_lm_states, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *node_off, const int64_t *level_off, const int32_t *node_time, const int32_t *node_state,
+    const int64_t *src_global, const int64_t *lat_arc, const int32_t *level_ptr, const int32_t *level_node,
+    const int32_t *in_ptr, const int32_t *in_arc, int64_t num_graph_arcs, const int32_t *arc_olabel, int start,
+    int64_t lm_states, int64_t lm_arcs, const int32_t *lm_ptr, const int32_t *lm_label, const int32_t *lm_dst,
+    const double *lm_weight, const int32_t *lm_bo_dst, const double *lm_bo_w, int lm_start, const int64_t *label_map,
+    int64_t label_map_len, double oov_cost, int32_t *out_count, int32_t *out_status, void *workspace,
+    int64_t workspace_bytes, void *stream);
+int asr_lattice_lmrescore_emit(
+    int B, int b_begin, int b_count, int max_lm_states, int64_t N, int64_t A, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *src_global, const int64_t *dst_global, const int64_t *arc_utt,
+    const int64_t *lat_arc, const float *lat_lp, const double *own_scale, int64_t num_graph_arcs,
+    const int32_t *arc_olabel, const float *arc_weight, int64_t lm_states, int64_t lm_arcs, const int32_t *lm_ptr,
+    const int32_t *lm_label, const int32_t *lm_dst, const double *lm_weight, const int32_t *lm_bo_dst,
+    const double *lm_bo_w, int lm_start, const int64_t *label_map, int64_t label_map_len, double oov_cost,
+    double scale, const int32_t *count, const int64_t *node_slot, const int64_t *arc_slot, int64_t E, int64_t M,
+    int32_t *out_lm_state, int32_t *out_src, int32_t *out_dst, int32_t *out_src_lm_state, double *out_lm_cost,
+    float *out_weight, float *out_acoustic, int32_t *out_ok, const void *workspace, int64_t workspace_bytes,
+    void *stream);
+int asr_lattice_lmrescore_sweep(
+    int B, int64_t E, int64_t M, int64_t EL, int64_t N, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr,
+    const int32_t *in_arc, const int32_t *out_ptr, const int32_t *src, const int32_t *dst, const float *weight,
+    const float *acoustic, const int32_t *lat_node, const int32_t *lm_state, const int32_t *node_time,
+    const int32_t *node_state, const int32_t *num_frames, const int32_t *reached_final, int64_t num_states,
+    const float *final_cost, int start, int64_t lm_states, const double *lm_final_star, int lm_start, double scale,
+    double lattice_beam, int threads, float *out_alpha, float *out_beta, int32_t *out_keep, float *out_best,
+    int32_t *out_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,9 @@ _WARNED = {}
 
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
+# the LM of asr_lattice_lmrescore_*: states, arcs, six CSR / back-off arrays, start, label map and length, oov cost
+_LM_ARGS = [_i64, _i64] + [_vp] * 6 + [_i, _vp, _i64, ctypes.c_double]
+
 _SIGNATURES = {
     'asr_abi_version': (ctypes.c_int, []),
     'asr_strerror': (ctypes.c_char_p, [_i]),
@@ -103,6 +106,14 @@ _SIGNATURES = {
     'asr_lattice_mbr_f64': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
                             [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 4 + [_i, _i, _i64] + [_vp] * 11 +
                             [_vp, _i64, _vp]),
+    'asr_lattice_lmrescore_supported': (_i, [_i64, _i64, _i64, _i]),
+    'asr_lattice_lmrescore_workspace_bytes': (_i64, [_i64, _i]),
+    'asr_lattice_lmrescore_expand': (_i, [_i] * 4 + [_i64] * 3 + [_vp] * 11 + [_i64, _vp, _i] + _LM_ARGS + [_vp] * 3 +
+                                     [_i64, _vp]),
+    'asr_lattice_lmrescore_emit': (_i, [_i] * 4 + [_i64] * 2 + [_vp] * 8 + [_i64] + [_vp] * 2 + _LM_ARGS +
+                                   [ctypes.c_double] + [_vp] * 3 + [_i64] * 2 + [_vp] * 9 + [_i64, _vp]),
+    'asr_lattice_lmrescore_sweep': (_i, [_i] + [_i64] * 4 + [_vp] * 18 + [_i64, _vp, _i, _i64, _vp, _i,
+                                    ctypes.c_double, ctypes.c_double, _i] + [_vp] * 6),
     'asr_split_bf16_f32': (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     'asr_log_softmax_shift_bwd_split_blocks': (_i, [_i64]),
     'asr_log_softmax_shift_bwd_split_bf16': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp]),

@@ -511,6 +511,32 @@ class DeviceLatticeBatch(object):
         self.launches = launches
         return out
 
+    # ---- rescoring with a back-off n-gram LM --------------------------------------------------
+    def rescore_lm(self, lm, label_map=None, scale=1.0, lattice_beam=None, oov_cost=INF, max_lm_states=None,
+                   workspace_bytes=None):
+        """lattice o LM (Kaldi's lattice-lmrescore under the back-off reading): another DeviceLatticeBatch
+        on this device over a RescoredGraph of its own, with alpha, beta and cost recomputed, so best_paths,
+        nbest, sentences, posteriors and mbr run on it unchanged.  att_speech.lattice_lm states the semantics
+        (DESIGN.md section 4.24).
+
+        lm: a BackoffLm, an LmFst or a file name; label_map: output label of the graph -> label of the LM
+        (None: matched by name when both have symbol tables, else the identity; lattice_lm.lm_label_map for
+        graphs of DecodingGraph.from_graph_generator); scale multiplies the LM costs (-1 takes a first-pass
+        LM out, approximately: the first pass treated back-off arcs as ordinary epsilons); lattice_beam
+        prunes against the new best (None: everything on a complete finite path); oov_cost: the cost of an
+        arc whose word the LM does not know (inf drops it).
+
+        On a GPU: asr_lattice_lmrescore_expand / _emit per launch (several launches when workspace_bytes,
+        default the batch's, does not hold 4 max_lm_states bytes per node at once) and one
+        asr_lattice_lmrescore_sweep; self.launches counts them.  An utterance with more than max_lm_states
+        (default 256, at most 1024) LM states on one node is redone by the numpy twin, with one warning per
+        call.  A batch of CPU tensors and ASR_LATTICE_RESCORE_NATIVE=0 (read per call) run the twin: the
+        same bits.  result.stats: max_lm_states, nodes_in, nodes_out, arcs_in, arcs_out, dropped_arcs,
+        redone_on_host."""
+        from att_speech.lattice_lm import rescore_device_batch
+        return rescore_device_batch(self, lm, label_map, scale, lattice_beam, oov_cost, max_lm_states,
+                                    workspace_bytes)
+
     # ---- the log-semiring pass ----------------------------------------------------------------
     def posteriors(self, acoustic_scale=None, lm_scale=1.0, workspace_bytes=None):
         """Arc and node posteriors under the path weights exp(-(sum of x + lm_scale * end)), x and end

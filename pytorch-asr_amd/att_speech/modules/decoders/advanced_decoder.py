@@ -604,7 +604,8 @@ class FSTDecoder(_ProjectionDecoder):
                  numerator_red='logsumexp', denominator_red='logsumexp',
                  embedder='LutLinear', embedder_kwargs={}, decode_beam=None,
                  decode_lattice_beam=None, decode_nbest=1, decode_confidence=False,
-                 decode_nbest_device=False, decode_mbr=False, **kwargs):
+                 decode_nbest_device=False, decode_mbr=False, decode_rescore_lm=None,
+                 decode_rescore_old_lm=None, decode_rescore_beam=None, **kwargs):
         super(FSTDecoder, self).__init__(**kwargs)
         # decode_beam: None = the exact every-state Viterbi below; a number = the beam-pruned
         # token-passing search (att_speech/wfst_decode.py) over the same graph with that beam
@@ -620,8 +621,19 @@ class FSTDecoder(_ProjectionDecoder):
         # decode_mbr: decode() also adds 'mbr': per utterance (labels, confidence, frames) of the
         # minimum-Bayes-risk label sequence at the search scale (DeviceLatticeBatch.mbr, one launch
         # per batch), and 'mbr_risk': its expected label edit distance under the lattice
+        # decode_rescore_lm (a file name or an LmFst): the lattices are rescored with this back-off n-gram LM
+        # where the search left them (DeviceLatticeBatch.rescore_lm, att_speech/lattice_lm.py), after
+        # decode_rescore_old_lm, if given, was taken out at scale -1; decode_rescore_beam prunes against the
+        # new best.  'decoded', 'nbest', 'word_confidence' and 'mbr' then come from the rescored lattices
         if decode_lattice_beam is not None and decode_beam is None:
             raise ValueError("decode_lattice_beam needs decode_beam: the lattice comes from the beam search")
+        if decode_rescore_lm is None and (decode_rescore_old_lm is not None or decode_rescore_beam is not None):
+            raise ValueError("decode_rescore_old_lm and decode_rescore_beam need decode_rescore_lm")
+        if decode_rescore_lm is not None and decode_lattice_beam is None:
+            raise ValueError("decode_rescore_lm needs decode_lattice_beam: it rescores the lattice")
+        self.decode_rescore_lm, self.decode_rescore_old_lm = decode_rescore_lm, decode_rescore_old_lm
+        self.decode_rescore_beam = decode_rescore_beam
+        self._rescore = None
         if decode_confidence and decode_lattice_beam is None:
             raise ValueError("decode_confidence needs decode_lattice_beam: the posteriors are the lattice's")
         if decode_mbr and decode_lattice_beam is None:
@@ -737,12 +749,16 @@ class FSTDecoder(_ProjectionDecoder):
             res = wfst_decode.decode_graph(logits.detach().float(), encoded_lens, self._decoding_graph,
                                            beam=float(self.decode_beam))
             ret = {'decoded': res['words'], 'logits': logits}   # the labels on the winning arcs
+            rescore = getattr(self, 'decode_rescore_lm', None) is not None
             if self.decode_lattice_beam is not None and (self.decode_confidence or self.decode_nbest_device
-                                                         or getattr(self, 'decode_mbr', False)):
+                                                         or getattr(self, 'decode_mbr', False) or rescore):
                 from att_speech import lattice_dp
                 batch, _ = lattice_dp.decode_lattice_device(
                     logits.detach().float(), encoded_lens, self._decoding_graph, beam=float(self.decode_beam),
                     lattice_beam=float(self.decode_lattice_beam))
+                if rescore:
+                    batch = self._rescore_batch(batch)
+                    ret['decoded'] = [words for words, _, _, _ in batch.best_paths()[0]]
                 if self.decode_nbest_device:
                     ret['nbest'] = batch.nbest(self.decode_nbest)
                 else:
@@ -774,6 +790,22 @@ class FSTDecoder(_ProjectionDecoder):
         return self._finish_decode(ret, 'fst_loss', logits, encoded_lens, texts, text_lens,
                                    other_data_in_batch, return_texts_and_generated_loss,
                                    return_logits_text_diff, None)
+
+    def _rescore_batch(self, batch):
+        """the lattices of a batch with decode_rescore_old_lm taken out and decode_rescore_lm put in"""
+        from att_speech import lattice_lm
+        gg = self.graph_generator
+        if self._rescore is None:
+            def load(lm):
+                lm = lattice_lm.BackoffLm.from_fst(lm)
+                return lm, lattice_lm.lm_label_map(lm, gg.vocabulary, gg.num_symbols)
+            old = self.decode_rescore_old_lm
+            self._rescore = (load(old) if old is not None else None, load(self.decode_rescore_lm))
+        old, (new, new_map) = self._rescore
+        if old is not None:
+            batch = batch.rescore_lm(old[0], label_map=old[1], scale=-1.0)
+        beam = self.decode_rescore_beam
+        return batch.rescore_lm(new, label_map=new_map, lattice_beam=None if beam is None else float(beam))
 
     def align(self, encoded, encoded_lens, texts, text_lens, **other):
         """Forced alignment of the transcripts to this decoder's own logits(encoded,

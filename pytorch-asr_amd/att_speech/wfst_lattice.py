@@ -316,6 +316,18 @@ class LatticeBatch(object):
         """Lattice.best_path for every lattice: a list of (words, cost, graph_cost, acoustic_cost)"""
         return self._best_paths(acoustic_scale, lm_scale)[0]
 
+    def rescore_lm(self, lm, label_map=None, scale=1.0, lattice_beam=None, oov_cost=INF, max_lm_states=None,
+                   workspace_bytes=None, graph=None):
+        """lattice o back-off n-gram LM: a LatticeBatch over a RescoredGraph, with `stats`.  The numpy twin
+        of DeviceLatticeBatch.rescore_lm, bit for bit (att_speech.lattice_lm states the semantics;
+        max_lm_states and workspace_bytes only bound the device path)."""
+        from att_speech.lattice_lm import rescore_lattices
+        lats, stats = rescore_lattices(self.lattices, lm, label_map, scale, lattice_beam, oov_cost, max_lm_states,
+                                       graph=graph)
+        out = LatticeBatch(lats)
+        out.stats = stats
+        return out
+
     def _best_paths(self, acoustic_scale=None, lm_scale=1.0):
         """(best_paths' list, per utterance the batch arc indices of the path's word-bearing arcs)"""
         none = ([], INF, INF, INF)

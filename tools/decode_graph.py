@@ -4,7 +4,8 @@ reference's scoring recipe (egs/wsj/ctc_kaldi_decode.sh:141-147) without Kaldi.
 
     python tools/decode_graph.py LOGPROBS.ark GRAPH.fst [--words words.txt] [--beam 16]
         [--acoustic-scale 1.0] [--batch 64] [--device cuda:0|cpu] [--out FILE]
-        [--lattice-beam X --nbest N [--device-nbest] [--acwt-sweep LO:HI:STEP] [--post OUT.npz] [--mbr OUT]]
+        [--lattice-beam X --nbest N [--device-nbest] [--acwt-sweep LO:HI:STEP] [--post OUT.npz] [--mbr OUT]
+         [--rescore-lm NEW.fst [--old-lm OLD.fst] [--rescore-beam X]]]
 
 LOGPROBS.ark: the float-matrix archive att_speech.ctc_forward writes (one [frames, classes] matrix
 per utterance).  GRAPH.fst: an OpenFst binary (vector/standard, plain or gzip) or an AT&T text
@@ -24,7 +25,11 @@ frame-level class posteriors of every lattice (lattice-to-post) go to OUT.npz, o
 [frames, classes] float32 matrix per utterance key, and nothing else is written.  With --mbr OUT
 every lattice is decoded by minimum Bayes risk (DeviceLatticeBatch.mbr: lattice-mbr-decode, one launch
 per batch): `uttid w1 w2 ...` lines go to OUT and `uttid word frame confidence` rows to OUT.conf, and
-nothing else is written."""
+nothing else is written.  With --rescore-lm NEW.fst every lattice is first rescored with that back-off n-gram
+LM where the search left it (DeviceLatticeBatch.rescore_lm: lattice-lmrescore under the back-off reading), after
+--old-lm OLD.fst, the LM compiled into the graph, was taken out at scale -1; --rescore-beam prunes against the
+new best.  The graph's output symbols are matched to the LM's input symbols by name when both files carry
+tables, else by number.  Every lattice output above then reads the rescored lattices."""
 import argparse
 import os
 import sys
@@ -67,25 +72,40 @@ def _lattices(graph, utts, device, batch, **kw):
             yield k, lat
 
 
+def make_rescorer(new_lm, old_lm=None, beam=None):
+    """DeviceLatticeBatch -> DeviceLatticeBatch: old_lm out at scale -1 (when given), new_lm in"""
+    from att_speech.lattice_lm import BackoffLm
+    new = BackoffLm.from_fst(new_lm)
+    old = BackoffLm.from_fst(old_lm) if old_lm is not None else None
+
+    def rescore(batch):
+        if old is not None:
+            batch = batch.rescore_lm(old, scale=-1.0)
+        return batch.rescore_lm(new, lattice_beam=beam)
+    return rescore
+
+
 def _tokens(table, words):
     return [table.find(int(w)) or str(w) for w in words] if table else [str(w) for w in words]
 
 
 def write_nbest(graph, utts, path, beam, lattice_beam, nbest, acoustic_scale=1.0, allow_partial=True,
-                device='cpu', batch=64, table=None, device_nbest=False):
+                device='cpu', batch=64, table=None, device_nbest=False, rescore=None):
     """`uttid-k cost w1 w2 ...`: the nbest cheapest distinct word sequences of every utterance;
     device_nbest: listed by DeviceLatticeBatch.nbest, a batch at a time"""
     kw = dict(beam=beam, lattice_beam=lattice_beam, acoustic_scale=acoustic_scale, allow_partial=allow_partial)
 
     def lists():
-        if not device_nbest:
+        if not device_nbest and rescore is None:
             for key, lat in _lattices(graph, utts, device, batch, **kw):
                 yield key, lat.nbest(nbest)
             return
         from att_speech.lattice_dp import decode_lattice_device
         for keys, lp, lens in _batches(utts, batch):
             every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, **kw)
-            for key, row in zip(keys, every.nbest(nbest)):
+            every = rescore(every) if rescore else every
+            rows = every.nbest(nbest) if device_nbest else [lat.nbest(nbest) for lat in every.lattices()]
+            for key, row in zip(keys, rows):
                 yield key, row
     out = open(path, 'w') if path else sys.stdout
     try:
@@ -98,7 +118,7 @@ def write_nbest(graph, utts, path, beam, lattice_beam, nbest, acoustic_scale=1.0
 
 
 def write_sweep(graph, utts, path, beam, lattice_beam, scales, acoustic_scale=1.0, allow_partial=True,
-                device='cpu', batch=64, table=None):
+                device='cpu', batch=64, table=None, rescore=None):
     """`scale uttid cost w1 w2 ...`: the best path of every utterance at every scale, from one search"""
     from att_speech.lattice_dp import decode_lattice_device
     rows = [[] for _ in scales]
@@ -106,6 +126,7 @@ def write_sweep(graph, utts, path, beam, lattice_beam, scales, acoustic_scale=1.
         every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, beam=beam,
                                          lattice_beam=lattice_beam, acoustic_scale=acoustic_scale,
                                          allow_partial=allow_partial)
+        every = rescore(every) if rescore else every
         for row, best in zip(rows, every.best_paths(scales)):
             row.extend(zip(keys, best))
     out = open(path, 'w') if path else sys.stdout
@@ -119,7 +140,7 @@ def write_sweep(graph, utts, path, beam, lattice_beam, scales, acoustic_scale=1.
 
 
 def write_post(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_partial=True, device='cpu',
-               batch=64, table=None):
+               batch=64, table=None, rescore=None):
     """OUT.npz: per utterance key the [frames, classes] posteriors of its lattice at the search's scales"""
     from att_speech.lattice_dp import decode_lattice_device
     mats = {}
@@ -127,6 +148,7 @@ def write_post(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_
         every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, beam=beam,
                                          lattice_beam=lattice_beam, acoustic_scale=acoustic_scale,
                                          allow_partial=allow_partial)
+        every = rescore(every) if rescore else every
         post = every.posteriors().frame_posteriors().cpu().numpy()
         for j, key in enumerate(keys):
             mats[key] = post[:lens[j], j]
@@ -134,7 +156,7 @@ def write_post(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_
 
 
 def write_mbr(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_partial=True, device='cpu',
-              batch=64, table=None):
+              batch=64, table=None, rescore=None):
     """OUT: `uttid w1 w2 ...`, the minimum-Bayes-risk word sequence of every lattice at the search's
     scales; OUT.conf: `uttid word frame confidence`, a row per word"""
     from att_speech.lattice_dp import decode_lattice_device
@@ -143,6 +165,7 @@ def write_mbr(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_p
             every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, beam=beam,
                                              lattice_beam=lattice_beam, acoustic_scale=acoustic_scale,
                                              allow_partial=allow_partial)
+            every = rescore(every) if rescore else every
             for key, res in zip(keys, every.mbr()):
                 tokens = _tokens(table, res.words)
                 out.write(' '.join([key] + tokens) + '\n')
@@ -168,9 +191,14 @@ def main(argv=None):
     ap.add_argument('--acwt-sweep', default=None, help='LO:HI:STEP: the 1-best per acoustic scale from one search')
     ap.add_argument('--post', default=None, help='OUT.npz: frame-level class posteriors of every lattice')
     ap.add_argument('--mbr', default=None, help='OUT: minimum-Bayes-risk transcripts; OUT.conf: word confidences')
+    ap.add_argument('--rescore-lm', default=None, help='NEW.fst: rescore every lattice with this back-off n-gram LM')
+    ap.add_argument('--old-lm', default=None, help='OLD.fst: the LM compiled into the graph, taken out first')
+    ap.add_argument('--rescore-beam', type=float, default=None, help='prune the rescored lattices against their best')
     a = ap.parse_args(argv)
-    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post or a.device_nbest or a.mbr):
-        ap.error('--nbest, --device-nbest, --acwt-sweep, --post and --mbr need --lattice-beam')
+    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post or a.device_nbest or a.mbr or a.rescore_lm):
+        ap.error('--nbest, --device-nbest, --acwt-sweep, --post, --mbr and --rescore-lm need --lattice-beam')
+    if a.rescore_lm is None and (a.old_lm or a.rescore_beam is not None):
+        ap.error('--old-lm and --rescore-beam need --rescore-lm')
     from att_speech import wfst_decode
     from att_speech.ctc_forward import read_kaldi_float_matrices
     from att_speech.lm_fst import SymbolTable
@@ -183,6 +211,8 @@ def main(argv=None):
         utts = [(k, mats[k]) for k in keys]
         kw = dict(beam=a.beam, lattice_beam=a.lattice_beam, acoustic_scale=a.acoustic_scale,
                   allow_partial=not a.no_allow_partial, device=device, batch=a.batch, table=table)
+        if a.rescore_lm:
+            kw['rescore'] = make_rescorer(a.rescore_lm, a.old_lm, a.rescore_beam)
         if a.mbr:
             write_mbr(graph, utts, a.mbr, **kw)
         elif a.post:
