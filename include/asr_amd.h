@@ -1443,6 +1443,62 @@ int asr_lattice_mbr_f64(
     void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * asr_lattice_oracle_i32: the lattice oracle of every lattice of such a batch in one launch (csrc/
+ * lattice_oracle.hip; Kaldi's lattice-oracle; LatticeBatch.oracle of
+ * att_speech/wfst_lattice.py is its numpy twin and gives the same results with ==): the complete path whose
+ * words are nearest to a reference in word edit distance.  Additions: the ABI version stays 24.  The batch,
+ * b_begin / b_count, x and end(v) as above; threads: 64, 128 or 256 lanes per workgroup, 0 = 256;
+ * acoustic_scale NaN: own_scale.
+ *
+ * Lattice model, per utterance, as for asr_lattice_mbr_f64: the start node s is the node (time 0, state
+ * `start`), arcs into it are ignored; v is an end node when end(v) < inf; an arc's word w is the olabel of its
+ * graph arc, 0 = no word.  The reference r_1..r_R: ref_num_words[b] = R labels > 0 at ref_words + b max_words
+ * (labels the graph does not have can only be substituted or deleted).
+ * Arithmetic: int32; U = 2^30 stands for unreachable and every sum is clamped with min(., U); supported only
+ *   if levels + max_words < U (asr_lattice_oracle_supported).
+ * Forward: D(s, q) = q for q = 0..R.  Every other node v in level order, per in-arc j = (u -> v, w) in the
+ *   stored in_arc order: w == 0: c_j(q) = D(u, q); else c_j(0) = D(u, 0) + 1 and for q >= 1
+ *   c_j(q) = min(D(u, q-1) + (w != r_q), D(u, q) + 1).  D0(v, q) = min_j c_j(q) (U without in-arcs);
+ *   D(v, q) = min(D0(v, q), D(v, q-1) + 1) = q + min_{i <= q} (D0(v, i) - i).
+ * Result: errors = min over the end nodes of D(v, R), v* the smallest node among the minima (the tie rule of
+ *   asr_lattice_bestpath_f64); no result (out_errors = -1, counts and words 0, cost +inf) without nodes, start
+ *   node or end node, or when the minimum is >= U.
+ * Traceback from (v*, R).  At (v, q), v != s: the first in-arc in the stored order with c_j(q) == D(v, q);
+ *   if w != 0, q >= 1 and D(u, q-1) + (w != r_q) == D(v, q): a diagonal step (correct when w == r_q, else a
+ *   substitution), ref_frames[q-1] = time(v), on to (u, q-1); else if w != 0: an insertion, on to (u, q);
+ *   else on to (u, q).  If no in-arc attains D(v, q): a deletion, ref_frames[q-1] = -1, on to (v, q-1).  At s
+ *   the remaining q positions are deletions.  errors = sub + ins + del and cor + sub + del = R.  Ties among
+ *   paths of the least distance are broken by this rule, not by cost.
+ *   ref_words [B, max_words] i32, ref_num_words [B] i32 (outside 0 .. max_words: status bit 1); max_words:
+ *   1 .. ASR_LATTICE_ORACLE_MAX_WORDS.  out_errors [B] i32; out_counts [B, 4] i32: substitutions, insertions,
+ *   deletions, correct; out_num_words [B] and out_words [L] i32: the non-zero olabels of the path in forward
+ *   order, utterance b's at level_off[b] (the kernel keeps the path's arcs there meanwhile);
+ *   out_ref_frames [B, max_words] i32; out_cost [B] f64: the path's cost summed forwards as the read-out of
+ *   asr_lattice_nbest_f64 sums it, g = 0, g = fl(g + x_j) per arc, then fl(g + fl(lm end(v*)));
+ *   out_status [B] i32 bit 1: an index out of range or a level that does not rise.
+ *   workspace: asr_lattice_oracle_workspace_bytes(nodes of the launch, max_words) = 4 (max_words + 1) bytes
+ *   per node, rounded: the rows D(v, .), kept for the traceback.  One workgroup per utterance; a wave owns a
+ *   node of a level and takes its in-arcs in turn, its lanes run over q in rounds of 64; the chain is a prefix
+ *   minimum over the lanes with a carry between the rounds; the traceback is one wave's, a lane per in-arc, the
+ *   first hit by ballot; workgroup barriers only, no atomics on global memory: two runs give the same words.
+ */
+#define ASR_LATTICE_ORACLE_MAX_WORDS 1023
+int asr_lattice_oracle_supported(int64_t N, int64_t A, int64_t L, int max_words);
+int64_t asr_lattice_oracle_workspace_bytes(int64_t num_nodes, int max_words);
+int asr_lattice_oracle_i32(
+    int B, int b_begin, int b_count, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
+    const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
+    const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
+    const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
+    double acoustic_scale, double lm_scale, int64_t num_states, int64_t num_graph_arcs, const float *arc_weight,
+    const int32_t *arc_olabel, const float *final_cost, int start, int threads, const int32_t *ref_words,
+    const int32_t *ref_num_words, int max_words, int32_t *out_errors, int32_t *out_counts, int32_t *out_num_words,
+    int32_t *out_words, int32_t *out_ref_frames, double *out_cost, int32_t *out_status, void *workspace,
+    int64_t workspace_bytes, void *stream);
+
+/*
  * asr_lattice_lmrescore_*: lattice o back-off n-gram LM for a batch that stays on the device
  * (csrc/lattice_lm.hip; att_speech/lattice_lm.py states the semantics and holds the
  * numpy twin, which gives the same bits).  Three entries, called in this order for the utterances

@@ -9,7 +9,9 @@ lattice-to-post).  DESIGN.md section 4.21.  `nbest` / `sentences` list its n che
 sequences, the hand-over to AttentionDecoderTCN.score_sentences, in one launch (section 4.22).  `mbr`
 decodes it by minimum Bayes risk (the word sequence of the least expected word edit distance, with
 per-word confidences and the confusion network) and `expected_errors` scores given sentences by that
-distance, all iterations in one launch of asr_lattice_mbr_f64 (section 4.23).
+distance, all iterations in one launch of asr_lattice_mbr_f64 (section 4.23).  `oracle` finds the path nearest
+to a reference in word edit distance (lattice-oracle) in one launch of asr_lattice_oracle_i32 (section 4.25),
+and `depth` is lattice-depth.
 
 A batch on a GPU runs asr_lattice_bestpath_f64 / asr_lattice_posterior_f64 / asr_lattice_nbest_f64
 (csrc/lattice_dp.hip); a batch of CPU tensors, or ASR_LATTICE_DP_NATIVE=0 (ASR_LATTICE_NBEST_NATIVE=0
@@ -25,13 +27,14 @@ import torch
 
 from att_speech import _native
 from att_speech.wfst_decode import DEFAULT_WORKSPACE_BYTES
-from att_speech.wfst_lattice import (INF, MBR_NONE, OVERFLOW_NAMES, Lattice, LatticeBatch, LatticePosteriors,
-                                     MBRResult, _decode_device, _order, _validate, decode_lattice_host, mbr_sausage,
-                                     nbest_lists)
+from att_speech.wfst_lattice import (INF, MBR_NONE, ORACLE_NONE, OVERFLOW_NAMES, Lattice, LatticeBatch,
+                                     LatticePosteriors, MBRResult, OracleResult, _decode_device, _oracle_references,
+                                     _order, _validate, decode_lattice_host, mbr_sausage, nbest_lists)
 
-THREADS_PER_WORKGROUP = 0       # 0: the kernels' default (64; nbest and mbr: 256); 64 / 128 / 256 for timing runs
+THREADS_PER_WORKGROUP = 0       # 0: the kernels' default (64; nbest, mbr and oracle: 256); 64 / 128 / 256 for timing runs
 NBEST_DEVICE_MAX = 64           # ASR_LATTICE_NBEST_MAX of include/asr_amd.h: a list entry per lane of a wave
 MBR_DEVICE_MAX_WORDS = 255      # ASR_LATTICE_MBR_MAX_WORDS: the longest hypothesis asr_lattice_mbr_f64 has columns for
+ORACLE_DEVICE_MAX_WORDS = 1023  # ASR_LATTICE_ORACLE_MAX_WORDS: the longest reference asr_lattice_oracle_i32 has columns for
 MBR_SAUSAGE_ENTRIES = 0         # sausage entries an utterance in mbr's buffer; 0: per slot a word of the graph each, at most 64
 
 
@@ -510,6 +513,97 @@ class DeviceLatticeBatch(object):
                     out[b].append(res[b].risk)
         self.launches = launches
         return out
+
+    # ---- the lattice oracle ------------------------------------------------------------------------
+    def oracle(self, references, acoustic_scale=None, lm_scale=1.0, workspace_bytes=None):
+        """The lattice oracle (Kaldi's lattice-oracle): per utterance the complete path whose words are nearest
+        to the reference (a list of labels > 0 per utterance) in word edit distance, one OracleResult each
+        (errors, substitutions, insertions, deletions, correct, words, ref_frames, cost; ORACLE_NONE where the
+        lattice has no complete path); the semantics are LatticeBatch.oracle's (DESIGN.md section 4.25,
+        include/asr_amd.h), and so are the results, with ==.  oracle_error_rate sums them up.
+
+        On a GPU all utterances are one launch of asr_lattice_oracle_i32, or several when workspace_bytes
+        (default: the batch's) does not hold 4 (max_words + 1) bytes per node at once, max_words being the
+        longest reference of the call; self.launches counts them.  A batch of CPU tensors and
+        ASR_LATTICE_ORACLE_NATIVE=0 (read per call) run LatticeBatch.oracle on a copy; so do, with one warning
+        per call, the utterances whose reference is longer than ORACLE_DEVICE_MAX_WORDS."""
+        B = self.num_utterances
+        refs = _oracle_references(references, B)
+        self.launches = 0
+        native = self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_ORACLE_NATIVE', '1') != '0'
+        if not native:
+            return self._host_batch().oracle(refs, acoustic_scale, lm_scale)
+        if B == 0 or self.num_nodes == 0:
+            return [ORACLE_NONE] * B
+        limit = max(1, min(int(ORACLE_DEVICE_MAX_WORDS), 1023))
+        redo = [b for b, r in enumerate(refs) if len(r) > limit]
+        W = max([1] + [len(r) for r in refs if len(r) <= limit])
+        L = _native.lib()
+        if not L.asr_lattice_oracle_supported(self.num_nodes, self.num_arcs, self.num_levels, W):
+            raise NotImplementedError("asr_lattice_oracle_i32: the batch is too large")
+        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
+        dev, p = self.device, _native._p
+        chunks = self._utterance_chunks(4 * (W + 1), budget - 64)
+        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
+        nbytes = L.asr_lattice_oracle_workspace_bytes(biggest, W)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rows = np.zeros((B, W), np.int32)
+        counts = np.zeros(B, np.int32)
+        for b, r in enumerate(refs):
+            if len(r) <= limit:                 # the others: an empty reference here, redone on the host below
+                rows[b, :len(r)] = r
+                counts[b] = len(r)
+        ref_w, ref_n = torch.from_numpy(rows).to(dev), torch.from_numpy(counts).to(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        small = torch.zeros((7, B), **i32)              # errors, status, words, then sub, ins, del, cor as [B, 4]
+        counts_d = small[3:].reshape(B, 4)
+        words = torch.zeros(max(1, self.num_levels), **i32)
+        frames = torch.zeros((B, W), **i32)
+        cost = torch.full((B,), INF, dtype=torch.float64, device=dev)
+        head, tail = self._common_args()
+        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
+        for b0, b1 in chunks:
+            self._check(L.asr_lattice_oracle_i32(
+                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(ref_w), p(ref_n), W, p(small[0]), p(counts_d),
+                p(small[2]), p(words), p(frames), p(cost), p(small[1]), p(ws), nbytes, _native._stream()),
+                'asr_lattice_oracle_i32')
+            self.launches += 1
+        small_h = small.cpu().numpy()
+        err_h, status_h, nw_h, ops_h = small_h[0], small_h[1], small_h[2], small_h[3:].reshape(B, 4)
+        if (status_h & 1).any():
+            raise ValueError("asr_lattice_oracle_i32: the batch's index arrays are inconsistent")
+        words_h, frames_h, cost_h = words.cpu().numpy(), frames.cpu().numpy(), cost.cpu().numpy()
+        out = []
+        for b in range(B):
+            if err_h[b] < 0:
+                out.append(ORACLE_NONE)
+                continue
+            o = int(self.level_off[b])
+            n_sub, n_ins, n_del, n_cor = (int(x) for x in ops_h[b])
+            out.append(OracleResult(int(err_h[b]), n_sub, n_ins, n_del, n_cor, words_h[o:o + nw_h[b]].tolist(),
+                                    frames_h[b, :len(refs[b])].tolist(), float(cost_h[b])))
+        if redo:
+            warnings.warn("oracle: %d of %d utterances have a reference of more than the device's %d words and "
+                          "were redone on the host" % (len(redo), B, limit))
+            lats = self._host_batch().lattices
+            sub = LatticeBatch([lats[b] for b in redo]).oracle([refs[b] for b in redo], acoustic_scale, lm_scale)
+            for b, r in zip(redo, sub):
+                out[b] = r
+        return out
+
+    def depth(self):
+        """per utterance the emitting lattice arcs per frame (Kaldi's lattice-depth), 0.0 for an empty lattice:
+        LatticeBatch.depth's numbers, counted with torch ops on the batch's device"""
+        B = self.num_utterances
+        if B == 0:
+            return []
+        arcs = torch.zeros(B, dtype=torch.int64, device=self.device)
+        if self.num_arcs:
+            arcs.index_add_(0, self.arc_utt, (self.ilabel != 0).long())
+        arcs = arcs.cpu().numpy()
+        nodes = np.diff(self.node_off)
+        return [float(int(arcs[b])) / float(self.num_frames[b]) if nodes[b] and self.num_frames[b] >= 1 else 0.0
+                for b in range(B)]
 
     # ---- rescoring with a back-off n-gram LM --------------------------------------------------
     def rescore_lm(self, lm, label_map=None, scale=1.0, lattice_beam=None, oov_cost=INF, max_lm_states=None,

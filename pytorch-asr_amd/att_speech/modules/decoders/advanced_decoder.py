@@ -605,7 +605,7 @@ class FSTDecoder(_ProjectionDecoder):
                  embedder='LutLinear', embedder_kwargs={}, decode_beam=None,
                  decode_lattice_beam=None, decode_nbest=1, decode_confidence=False,
                  decode_nbest_device=False, decode_mbr=False, decode_rescore_lm=None,
-                 decode_rescore_old_lm=None, decode_rescore_beam=None, **kwargs):
+                 decode_rescore_old_lm=None, decode_rescore_beam=None, decode_oracle=False, **kwargs):
         super(FSTDecoder, self).__init__(**kwargs)
         # decode_beam: None = the exact every-state Viterbi below; a number = the beam-pruned
         # token-passing search (att_speech/wfst_decode.py) over the same graph with that beam
@@ -624,7 +624,10 @@ class FSTDecoder(_ProjectionDecoder):
         # decode_rescore_lm (a file name or an LmFst): the lattices are rescored with this back-off n-gram LM
         # where the search left them (DeviceLatticeBatch.rescore_lm, att_speech/lattice_lm.py), after
         # decode_rescore_old_lm, if given, was taken out at scale -1; decode_rescore_beam prunes against the
-        # new best.  'decoded', 'nbest', 'word_confidence' and 'mbr' then come from the rescored lattices
+        # new best.  'decoded', 'nbest', 'word_confidence', 'mbr' and 'oracle' then come from the rescored lattices
+        # decode_oracle: when decode() is given texts / text_lens it also adds 'oracle': per utterance
+        # (errors, labels) of the lattice path nearest to texts[b, :text_lens[b]] in label edit distance
+        # (DeviceLatticeBatch.oracle, one launch per batch; errors -1: the lattice has no complete path)
         if decode_lattice_beam is not None and decode_beam is None:
             raise ValueError("decode_lattice_beam needs decode_beam: the lattice comes from the beam search")
         if decode_rescore_lm is None and (decode_rescore_old_lm is not None or decode_rescore_beam is not None):
@@ -639,6 +642,9 @@ class FSTDecoder(_ProjectionDecoder):
         if decode_mbr and decode_lattice_beam is None:
             raise ValueError("decode_mbr needs decode_lattice_beam: the risk is taken over the lattice")
         self.decode_mbr = bool(decode_mbr)
+        if decode_oracle and decode_lattice_beam is None:
+            raise ValueError("decode_oracle needs decode_lattice_beam: the oracle is taken over the lattice")
+        self.decode_oracle = bool(decode_oracle)
         self.decode_beam, self.decode_confidence = decode_beam, bool(decode_confidence)
         self.decode_lattice_beam, self.decode_nbest = decode_lattice_beam, int(decode_nbest)
         self.decode_nbest_device = bool(decode_nbest_device)
@@ -751,7 +757,8 @@ class FSTDecoder(_ProjectionDecoder):
             ret = {'decoded': res['words'], 'logits': logits}   # the labels on the winning arcs
             rescore = getattr(self, 'decode_rescore_lm', None) is not None
             if self.decode_lattice_beam is not None and (self.decode_confidence or self.decode_nbest_device
-                                                         or getattr(self, 'decode_mbr', False) or rescore):
+                                                         or getattr(self, 'decode_mbr', False) or rescore
+                                                         or getattr(self, 'decode_oracle', False)):
                 from att_speech import lattice_dp
                 batch, _ = lattice_dp.decode_lattice_device(
                     logits.detach().float(), encoded_lens, self._decoding_graph, beam=float(self.decode_beam),
@@ -770,6 +777,10 @@ class FSTDecoder(_ProjectionDecoder):
                     mbr = batch.mbr()
                     ret['mbr'] = [(r.words, r.confidence, r.frames) for r in mbr]
                     ret['mbr_risk'] = [r.risk for r in mbr]
+                if getattr(self, 'decode_oracle', False) and texts is not None and text_lens is not None:
+                    refs = [torch.as_tensor(t)[:int(l)].reshape(-1).tolist()
+                            for t, l in zip(texts, torch.as_tensor(text_lens).tolist())]
+                    ret['oracle'] = [(r.errors, r.words) for r in batch.oracle(refs)]
             elif self.decode_lattice_beam is not None:
                 from att_speech import wfst_lattice
                 lats, _ = wfst_lattice.decode_lattice(

@@ -181,6 +181,16 @@ class Lattice(object):
         """the word lists of nbest(n), the shape AttentionDecoderTCN.score_sentences takes"""
         return [w for w, _ in self.nbest(n, **kw)]
 
+    def oracle(self, reference, acoustic_scale=None, lm_scale=1.0):
+        """LatticeBatch.oracle of this lattice alone: one OracleResult"""
+        return LatticeBatch([self]).oracle([reference], acoustic_scale, lm_scale)[0]
+
+    def depth(self):
+        """emitting arcs per frame (Kaldi's lattice-depth); 0.0 for an empty lattice"""
+        if not self.num_nodes or self.num_frames < 1:
+            return 0.0
+        return float(int((self.ilabel != 0).sum())) / float(self.num_frames)
+
 
 NBEST_HASH_MUL = 0x9E3779B97F4A7C15     # H(o, h) = h * NBEST_HASH_MUL + o + 1 mod 2^64: LatticeBatch.nbest
 
@@ -235,6 +245,151 @@ def mbr_result(words, risk, iterations, table):
         frames.append(_mbr_frame(t, g))
     return MBRResult([int(w) for w in words], conf, frames, float(int(risk)) / MBR_ONE, int(iterations),
                      mbr_sausage(table))
+
+
+# the lattice oracle (LatticeBatch.oracle, asr_lattice_oracle_i32): word edit distances
+# are int32, ORACLE_UNREACHABLE stands for no path and every sum is clamped to it
+ORACLE_UNREACHABLE = 1 << 30
+
+OracleResult = collections.namedtuple('OracleResult', 'errors substitutions insertions deletions correct words '
+                                                      'ref_frames cost')
+OracleResult.__doc__ = """One utterance's lattice oracle: the least word edit distance `errors` between the reference
+and any complete path of the lattice, split into substitutions, insertions (path words matched to nothing) and
+deletions (reference words matched to nothing), with `correct` the matched words; `words` the word sequence of the
+chosen path, ref_frames per reference word the end time of the arc it was aligned to (-1: deleted), and cost the
+path's cost at the call's scales."""
+
+ORACLE_NONE = OracleResult(-1, 0, 0, 0, 0, [], [], INF)
+
+OracleErrorRate = collections.namedtuple('OracleErrorRate', 'errors reference_words rate skipped')
+
+
+def oracle_error_rate(results, references):
+    """(errors, reference_words, rate, skipped) over the utterances that have a result: the sums of their errors
+    and reference lengths and the ratio of the two (0.0 over no reference words); the ORACLE_NONE utterances are
+    left out of both sums and counted in `skipped`."""
+    results, references = list(results), list(references)
+    if len(results) != len(references):
+        raise ValueError("oracle_error_rate: one reference per result")
+    errors = words = skipped = 0
+    for res, ref in zip(results, references):
+        if res == ORACLE_NONE or res.errors < 0:
+            skipped += 1
+            continue
+        errors += int(res.errors)
+        words += len(ref)
+    return OracleErrorRate(errors, words, float(errors) / words if words else 0.0, skipped)
+
+
+def _oracle_references(references, B):
+    if len(references) != B:
+        raise ValueError("references must hold one word list per utterance")
+    refs = [[int(w) for w in r] for r in references]
+    if any(w <= 0 for r in refs for w in r):
+        raise ValueError("references hold word labels > 0")
+    return refs
+
+
+def _oracle_arc_rows(Du, w, ref):
+    """c_j(.) of in-arcs with source rows Du [k, R + 1] and words w [k] against the reference [R]"""
+    U = ORACLE_UNREACHABLE
+    step = np.minimum(Du + 1, U)
+    c = step.copy()
+    if Du.shape[1] > 1:
+        c[:, 1:] = np.minimum(np.minimum(Du[:, :-1] + (w[:, None] != ref[None, :]), U), step[:, 1:])
+    return np.where((w != 0)[:, None], c, Du)
+
+
+def _oracle_path(lat, ref):
+    """the oracle path of one Lattice against the labels `ref`: None, or (errors, (substitutions, insertions,
+    deletions, correct), ref_frames, the path's lattice arcs in forward order, its end node); the semantics
+    include/asr_amd.h states for asr_lattice_oracle_i32"""
+    U = ORACLE_UNREACHABLE
+    n, R, g = lat.num_nodes, len(ref), lat.graph
+    if not n:
+        return None
+    start = np.nonzero((lat.time == 0) & (lat.state == g.start))[0]
+    if not len(start):
+        return None
+    s = int(start[0])
+    level = lat.time.astype(np.int64) * (g.num_ranks + 1) + g.rank[lat.state]
+    order = np.argsort(level, kind='stable')
+    cuts = np.nonzero(np.r_[True, level[order][1:] != level[order][:-1]])[0]
+    if len(cuts) + R >= U:
+        raise ValueError("oracle: the levels of the lattice plus the reference must stay below 2^30")
+    src, dst, ol = lat.src.astype(np.int64), lat.dst.astype(np.int64), lat.olabel.astype(np.int64)
+    in_arc = np.argsort(dst, kind='stable')             # a node's in-arcs in arc order
+    in_ptr = np.searchsorted(dst[in_arc], np.arange(n + 1))
+    ref = np.asarray(ref, np.int64)
+    col = np.arange(R + 1, dtype=np.int64)
+    D = np.full((n, R + 1), U, np.int64)
+    D[s] = col
+    for a, b in zip(cuts, list(cuts[1:]) + [n]):
+        V = order[a:b]
+        V = V[(V != s) & (in_ptr[V + 1] > in_ptr[V])]
+        if not len(V):
+            continue
+        pos, owner = _ranges(in_ptr[V], in_ptr[V + 1])
+        arcs = in_arc[pos]
+        c = _oracle_arc_rows(D[src[arcs]], ol[arcs], ref)
+        first = np.nonzero(np.r_[True, owner[1:] != owner[:-1]])[0]
+        D0 = np.minimum.reduceat(c, first, axis=0)
+        D[V] = np.minimum(col + np.minimum.accumulate(D0 - col, axis=1), U)
+    at_n = lat.time == lat.num_frames
+    is_end = at_n & (g.final[lat.state] < INF) if lat.reached_final else at_n
+    ends = np.nonzero(is_end)[0]
+    if not len(ends) or int(D[ends, R].min()) >= U:
+        return None
+    errors = int(D[ends, R].min())
+    v = last = int(ends[np.nonzero(D[ends, R] == errors)[0][0]])
+    q = R
+    n_sub = n_ins = n_del = n_cor = 0
+    frames = [0] * R
+    path = []
+    while v != s:
+        js = in_arc[in_ptr[v]:in_ptr[v + 1]]
+        hit = np.nonzero(_oracle_arc_rows(D[src[js]], ol[js], ref)[:, q] == D[v, q])[0] if len(js) else []
+        if not len(hit):
+            frames[q - 1] = -1
+            n_del += 1
+            q -= 1
+            continue
+        j = int(js[hit[0]])
+        u, w = int(src[j]), int(ol[j])
+        path.append(j)
+        if w != 0 and q >= 1 and min(int(D[u, q - 1]) + (w != ref[q - 1]), U) == D[v, q]:
+            if w == ref[q - 1]:
+                n_cor += 1
+            else:
+                n_sub += 1
+            frames[q - 1] = int(lat.time[v])
+            q -= 1
+        elif w != 0:
+            n_ins += 1
+        v = u
+    for k in range(q):
+        frames[k] = -1
+    n_del += q
+    path.reverse()
+    return errors, (n_sub, n_ins, n_del, n_cor), frames, path, last
+
+
+def _oracle_one(lat, ref, acoustic_scale, lm_scale):
+    found = _oracle_path(lat, ref)
+    if found is None:
+        return ORACLE_NONE
+    errors, (n_sub, n_ins, n_del, n_cor), frames, path, last = found
+    g, ol = lat.graph, lat.olabel
+    sc = lat.acoustic_scale if acoustic_scale is None else float(acoustic_scale)
+    lm = float(lm_scale)
+    with np.errstate(invalid='ignore', over='ignore'):
+        x = lm * lat.w.astype(np.float64) - sc * lat.lp.astype(np.float64)
+        total = np.float64(0.0)
+        for j in path:
+            total = total + x[j]
+        end = np.float64(lm) * np.float64(g.final[lat.state[last]]) if lat.reached_final else np.float64(0.0)
+        cost = float(total + end)
+    return OracleResult(errors, n_sub, n_ins, n_del, n_cor, [int(ol[j]) for j in path if ol[j] != 0], frames, cost)
 
 
 class _Entries(object):
@@ -530,6 +685,28 @@ class LatticeBatch(object):
             arc = np.where((fwd[self.src] > -INF) & (bwd[self.dst] > -INF) & (za > -INF),
                            part + bwd[self.dst] - za, -INF)
         return LatticePosteriors(self, log_z, arc, node, acoustic_scale, lm_scale)
+
+    # ---- the lattice oracle ---------------------------------------------------------------------
+    def oracle(self, references, acoustic_scale=None, lm_scale=1.0):
+        """The lattice oracle (Kaldi's lattice-oracle): per utterance the complete path whose words are
+        nearest to the reference (a list of labels > 0) in word edit distance, as an OracleResult; ORACLE_NONE
+        where the lattice has no complete path.  The numpy twin of asr_lattice_oracle_i32 (include/asr_amd.h
+        states the semantics), in the same integer arithmetic, so both give the same
+        results with ==.
+
+        D(v, q), the least distance between the words of a path from the start node to v and the first q
+        reference labels, is computed level by level: per in-arc (u -> v, w) in arc order c(q) = D(u, q) for
+        w = 0, else min(D(u, q - 1) + [w != r_q], D(u, q) + 1); D0 = min over the in-arcs; D(v, q) =
+        min(D0(v, q), D(v, q - 1) + 1).  errors = min over the end nodes of D(v, R), the smallest node among
+        the minima; the traceback takes the first in-arc that attains D(v, q), a diagonal step before an
+        insertion, and a deletion only when no in-arc attains it.  Ties among paths of the least distance are
+        broken by that rule, not by cost; cost is summed forwards as nbest sums it."""
+        refs = _oracle_references(references, len(self.lattices))
+        return [_oracle_one(lat, ref, acoustic_scale, lm_scale) for lat, ref in zip(self.lattices, refs)]
+
+    def depth(self):
+        """per utterance the emitting arcs per frame (Kaldi's lattice-depth); 0.0 for an empty lattice"""
+        return [lat.depth() for lat in self.lattices]
 
     # ---- minimum-Bayes-risk decoding ---------------------------------------------------------
     def conditionals(self, acoustic_scale=None, lm_scale=1.0):

@@ -5,7 +5,7 @@ reference's scoring recipe (egs/wsj/ctc_kaldi_decode.sh:141-147) without Kaldi.
     python tools/decode_graph.py LOGPROBS.ark GRAPH.fst [--words words.txt] [--beam 16]
         [--acoustic-scale 1.0] [--batch 64] [--device cuda:0|cpu] [--out FILE]
         [--lattice-beam X --nbest N [--device-nbest] [--acwt-sweep LO:HI:STEP] [--post OUT.npz] [--mbr OUT]
-         [--rescore-lm NEW.fst [--old-lm OLD.fst] [--rescore-beam X]]]
+         [--rescore-lm NEW.fst [--old-lm OLD.fst] [--rescore-beam X]] [--oracle REF --oracle-out OUT]]
 
 LOGPROBS.ark: the float-matrix archive att_speech.ctc_forward writes (one [frames, classes] matrix
 per utterance).  GRAPH.fst: an OpenFst binary (vector/standard, plain or gzip) or an AT&T text
@@ -29,7 +29,12 @@ nothing else is written.  With --rescore-lm NEW.fst every lattice is first resco
 LM where the search left it (DeviceLatticeBatch.rescore_lm: lattice-lmrescore under the back-off reading), after
 --old-lm OLD.fst, the LM compiled into the graph, was taken out at scale -1; --rescore-beam prunes against the
 new best.  The graph's output symbols are matched to the LM's input symbols by name when both files carry
-tables, else by number.  Every lattice output above then reads the rescored lattices."""
+tables, else by number.  Every lattice output above then reads the rescored lattices.  With --oracle REF
+--oracle-out OUT (REF: `uttid w1 w2 ...` lines, symbols of --words or integers without it) every lattice, after
+--rescore-lm when given, is searched for the path nearest to its reference in word edit distance
+(DeviceLatticeBatch.oracle: lattice-oracle, one launch per batch): OUT gets `uttid errors sub ins del ref_len
+depth w1 w2 ...` rows (errors -1: the lattice has no complete path; depth: emitting arcs per frame,
+lattice-depth) and a last row `TOTAL errors ref_len rate mean_depth`, and nothing else is written."""
 import argparse
 import os
 import sys
@@ -173,6 +178,51 @@ def write_mbr(graph, utts, path, beam, lattice_beam, acoustic_scale=1.0, allow_p
                     conf.write('%s %s %d %.6f\n' % (key, tok, frame, c))
 
 
+def read_references(path, table=None):
+    """{uttid: [labels]} of `uttid w1 w2 ...` lines: symbols of `table`, or integers without one"""
+    refs = {}
+    with open(path) as f:
+        for line in f:
+            parts = line.split()
+            if not parts:
+                continue
+            if table is not None:
+                labels = [table.find(tok) for tok in parts[1:]]
+                if any(l <= 0 for l in labels):
+                    raise ValueError("%s: a word of %s is not in the symbol table" % (path, parts[0]))
+            else:
+                labels = [int(tok) for tok in parts[1:]]
+            refs[parts[0]] = labels
+    return refs
+
+
+def write_oracle(graph, utts, path, references, beam, lattice_beam, acoustic_scale=1.0, allow_partial=True,
+                 device='cpu', batch=64, table=None, rescore=None):
+    """OUT: `uttid errors sub ins del ref_len depth w1 w2 ...`, the lattice oracle of every utterance against
+    references[uttid], then `TOTAL errors ref_len rate mean_depth` over the utterances that have a path"""
+    from att_speech.lattice_dp import decode_lattice_device
+    from att_speech.wfst_lattice import oracle_error_rate
+    missing = [k for k, _ in utts if k not in references]
+    if missing:
+        raise ValueError("no reference for %d utterances, the first: %s" % (len(missing), missing[0]))
+    results, given, depths = [], [], []
+    with open(path, 'w') as out:
+        for keys, lp, lens in _batches(utts, batch):
+            every, _ = decode_lattice_device(torch.from_numpy(lp).to(device), lens, graph, beam=beam,
+                                             lattice_beam=lattice_beam, acoustic_scale=acoustic_scale,
+                                             allow_partial=allow_partial)
+            every = rescore(every) if rescore else every
+            refs = [references[k] for k in keys]
+            for key, ref, res, depth in zip(keys, refs, every.oracle(refs), every.depth()):
+                out.write(' '.join([key] + [str(v) for v in (res.errors, res.substitutions, res.insertions,
+                                                               res.deletions, len(ref))] + ['%.6f' % depth]
+                                   + _tokens(table, res.words)) + '\n')
+                results.append(res), given.append(ref), depths.append(depth)
+        total = oracle_error_rate(results, given)
+        out.write('TOTAL %d %d %.6f %.6f\n' % (total.errors, total.reference_words, total.rate,
+                                               float(np.mean(depths)) if depths else 0.0))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('logprobs')
@@ -194,9 +244,14 @@ def main(argv=None):
     ap.add_argument('--rescore-lm', default=None, help='NEW.fst: rescore every lattice with this back-off n-gram LM')
     ap.add_argument('--old-lm', default=None, help='OLD.fst: the LM compiled into the graph, taken out first')
     ap.add_argument('--rescore-beam', type=float, default=None, help='prune the rescored lattices against their best')
+    ap.add_argument('--oracle', default=None, help='REF: `uttid w1 w2 ...` reference transcripts')
+    ap.add_argument('--oracle-out', default=None, help='OUT: the lattice oracle of every utterance against REF')
     a = ap.parse_args(argv)
-    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post or a.device_nbest or a.mbr or a.rescore_lm):
-        ap.error('--nbest, --device-nbest, --acwt-sweep, --post, --mbr and --rescore-lm need --lattice-beam')
+    if a.lattice_beam is None and (a.acwt_sweep or a.nbest != 1 or a.post or a.device_nbest or a.mbr or a.rescore_lm
+                                   or a.oracle):
+        ap.error('--nbest, --device-nbest, --acwt-sweep, --post, --mbr, --rescore-lm and --oracle need --lattice-beam')
+    if (a.oracle is None) != (a.oracle_out is None):
+        ap.error('--oracle REF and --oracle-out OUT go together')
     if a.rescore_lm is None and (a.old_lm or a.rescore_beam is not None):
         ap.error('--old-lm and --rescore-beam need --rescore-lm')
     from att_speech import wfst_decode
@@ -213,7 +268,9 @@ def main(argv=None):
                   allow_partial=not a.no_allow_partial, device=device, batch=a.batch, table=table)
         if a.rescore_lm:
             kw['rescore'] = make_rescorer(a.rescore_lm, a.old_lm, a.rescore_beam)
-        if a.mbr:
+        if a.oracle:
+            write_oracle(graph, utts, a.oracle_out, read_references(a.oracle, table), **kw)
+        elif a.mbr:
             write_mbr(graph, utts, a.mbr, **kw)
         elif a.post:
             write_post(graph, utts, a.post, **kw)
