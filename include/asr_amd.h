@@ -539,6 +539,25 @@ int asr_conv1_7x7s2_fwd(const float *x, const float *w, int B, int T, int F, voi
                         double *chan_sums, void *workspace, int64_t workspace_bytes, void *stream);
 int asr_conv1_7x7s2_wgrad(const float *x, const void *dy, int B, int T, int F, float *dw,
                           void *workspace, int64_t workspace_bytes, void *stream);
+/*
+ * The same weight gradient with the backward pass of the BatchNorm + Hardtanh behind the
+ * convolution applied on the way in: dy is the gradient reaching the BatchNorm's OUTPUT, z the
+ * convolution's saved output (both y's layout), and the kernel forms, per element, what phase 2
+ * of asr_bn_act_bwd_phase_f32 would store as dx (same operations, same bits) without that
+ * tensor ever existing.  conv_bias (or null), gamma, beta, save_mean, save_invstd, training,
+ * lo, hi: as for asr_bn_act_bwd_phase_f32; bn_workspace: that call's workspace after its
+ * phase 1 (the two per-channel sums, possibly all-reduced); n_total: the element count the
+ * sums stand for.  asr_conv1_7x7s2_wgrad_bn_supported(F): 1 for the widths the fused kernel is
+ * built for (the others return ASR_EUNSUPPORTED and keep the two-kernel path).
+ * (Additions to ABI v24.)
+ */
+int asr_conv1_7x7s2_wgrad_bn_supported(int F);
+int asr_conv1_7x7s2_wgrad_bn(const float *x, const void *z, const void *dy, int B, int T, int F,
+                             const float *conv_bias, const float *gamma, const float *beta,
+                             const float *save_mean, const float *save_invstd,
+                             int training, float lo, float hi, const void *bn_workspace,
+                             double n_total, float *dw, void *workspace,
+                             int64_t workspace_bytes, void *stream);
 
 /* The same first convolution for the WSJ recipes' real features: x [B, T, F, cin] f32 — the
  * reference's bs x t x f x c layout (deep_speech_2.py:127), cin = 3 (static, delta,

@@ -60,6 +60,9 @@ _SIGNATURES = {
     'asr_conv1_7x7s2_workspace_bytes': (_i64, []),
     'asr_conv1_7x7s2_fwd': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     'asr_conv1_7x7s2_wgrad': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    'asr_conv1_7x7s2_wgrad_bn_supported': (_i, [_i]),
+    'asr_conv1_7x7s2_wgrad_bn': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f,
+                                      _vp, ctypes.c_double, _vp, _vp, _i64, _vp]),
     'asr_conv1c_7x7s2_workspace_bytes': (_i64, [_i]),
     'asr_conv1c_7x7s2_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     'asr_conv1c_7x7s2_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
@@ -1085,6 +1088,31 @@ def bn_act_bwd(x, gamma, beta, mean, invstd, training, lo, hi, dy, time_major=Fa
     return dx, dgamma, dbeta, dcb
 
 
+def bn_act_bwd_sums(x, gamma, beta, mean, invstd, training, lo, hi, dy, conv_bias=None):
+    """phase 1 of asr_bn_act_bwd_phase_f32 alone, for a consumer that applies phase 2 itself
+    (conv1_wgrad_bn): x, dy [B,C,H,W] channels-last bf16 -> (workspace holding the two
+    per-channel sums, as f64 in its first 2 C * 8 bytes; dgamma [C]; dbeta [C]; dconv_bias [C]
+    | None).  No dx is allocated."""
+    x = _nhwc_bf16(x, 'x')[0]
+    dy = _nhwc_bf16(dy, 'dy')[0]
+    B, C, H, W = x.shape
+    L = lib()
+    dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+    dcb = None
+    if conv_bias is not None:
+        conv_bias = _dev(conv_bias, torch.float32, 'conv_bias')
+        dcb = torch.empty(C, dtype=torch.float32, device=x.device)
+    nbytes = L.asr_bn_act_workspace_bytes(C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    # (dx must be a pointer; phase 1 stores nothing through it)
+    check(L.asr_bn_act_bwd_phase_f32(
+        _p(x), 1, _p(conv_bias), B, C, H, W, _p(gamma), _p(beta), _p(mean), _p(invstd), 1,
+        int(bool(training)), float(lo), float(hi), _p(dy), 1, 0, _p(ws), _p(dgamma), _p(dbeta),
+        _p(dcb), _p(ws), nbytes, 1, 0.0, _stream()), 'asr_bn_act_bwd_phase_f32')
+    return ws, dgamma, dbeta, dcb
+
+
 def tcn_attention_step(eproj, enc, enc_lens, filt, glob, w_score, b_score, temperature,
                        att_prev, parent, beam, window=None):
     """asr_tcn_attention_step_f32 -> (att_new [B*beam, T], context [B*beam, E]); with
@@ -1450,6 +1478,39 @@ def conv1_wgrad(x, dy):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         check(L.asr_conv1c_7x7s2_wgrad(_p(x), _p(dy), B, T, F, cin, _p(dw), _p(ws), nbytes, _stream()),
               'asr_conv1c_7x7s2_wgrad')
+    return dw
+
+
+def conv1_wgrad_bn_supported(F, cin=1):
+    """widths asr_conv1_7x7s2_wgrad_bn is built for (one input channel)"""
+    return cin == 1 and F >= 7 and bool(lib().asr_conv1_7x7s2_wgrad_bn_supported(int(F)))
+
+
+def conv1_wgrad_bn(x, z, dy, conv_bias, gamma, beta, mean, invstd, training, lo, hi, bn_ws, n_total):
+    """asr_conv1_7x7s2_wgrad_bn: x [B, T, F] f32, z (the convolution's output) and dy (the
+    gradient reaching the BatchNorm + Hardtanh's output) logical [B, 32, To, Fo] channels-last
+    bf16, bn_ws the workspace bn_act_bwd_sums left (its sums possibly all-reduced, standing for
+    n_total elements) -> dw [32, 1, 7, 7] f32: the weight gradient with the BatchNorm backward
+    applied on the way in, bit for bit bn_act_bwd's dx fed to conv1_wgrad."""
+    x = _dev(x, torch.float32, 'x')
+    if z.dtype != torch.bfloat16 or dy.dtype != torch.bfloat16:
+        raise TypeError('conv1_wgrad_bn: z and dy must be bfloat16')
+    z = _nhwc_bf16(z, 'z')[0]
+    dy = _nhwc_bf16(dy, 'dy')[0]
+    B, T, F = x.shape
+    if tuple(z.shape) != (B, 32, T + 6, (F - 7) // 2 + 1) or z.shape != dy.shape:
+        raise ValueError('conv1_wgrad_bn: z / dy must be [%d, 32, %d, %d]' % (B, T + 6, (F - 7) // 2 + 1))
+    if conv_bias is not None:
+        conv_bias = _dev(conv_bias, torch.float32, 'conv_bias')
+    dw = torch.empty((32, 1, 7, 7), dtype=torch.float32, device=x.device)
+    L = lib()
+    nbytes = L.asr_conv1_7x7s2_workspace_bytes()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    check(L.asr_conv1_7x7s2_wgrad_bn(
+        _p(x), _p(z), _p(dy), B, T, F, _p(conv_bias), _p(_dev(gamma, torch.float32, 'gamma')),
+        _p(_dev(beta, torch.float32, 'beta')), _p(mean), _p(invstd), int(bool(training)),
+        float(lo), float(hi), _p(bn_ws), float(n_total), _p(dw), _p(ws), nbytes, _stream()),
+        'asr_conv1_7x7s2_wgrad_bn')
     return dw
 
 

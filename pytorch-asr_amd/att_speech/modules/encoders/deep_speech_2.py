@@ -130,17 +130,23 @@ class DeepSpeech2(BaseEncoder):
             from att_speech.modules.encoders import native_conv
             c1 = conv[0]
             sums1 = sums2 = None                             # channel statistics from the conv epilogues
-            if bf16 and self.native_conv and native_conv.first_supported(c1, features):
-                x, sums1 = native_conv.conv1(features, c1)   # hand-written MFMA kernels
+            native1 = bf16 and self.native_conv and native_conv.first_supported(c1, features)
+            if native1 and native_conv.conv1_bn_supported(c1, features):
+                # conv1 + BatchNorm + Hardtanh as one node: its weight gradient applies the
+                # BatchNorm backward itself, no gradient tensor between the two
+                x = native_conv.conv1_bn_hardtanh(features, c1, conv[1].batch_norm, conv[2])
             else:
-                if bf16 and self.native_conv and not getattr(self, '_warned_conv1', False):
-                    self._warned_conv1 = True
-                    warnings.warn('DeepSpeech2: the first convolution is not a (1 or 3)->32 7x7 stride-(1,2) '
-                                  'shape on gradient-free features csrc/conv.hip is built for; using '
-                                  'torch / MIOpen for it')
-                x = run_conv(c1, features, with_bias=False, keep_bf16=True)
-            x = bn_hardtanh(x, conv[1].batch_norm, conv[2], out_bf16=bf16, conv_bias=c1.bias,
-                            chan_sums=sums1)
+                if native1:
+                    x, sums1 = native_conv.conv1(features, c1)   # hand-written MFMA kernels
+                else:
+                    if bf16 and self.native_conv and not getattr(self, '_warned_conv1', False):
+                        self._warned_conv1 = True
+                        warnings.warn('DeepSpeech2: the first convolution is not a (1 or 3)->32 7x7 stride-(1,2) '
+                                      'shape on gradient-free features csrc/conv.hip is built for; using '
+                                      'torch / MIOpen for it')
+                    x = run_conv(c1, features, with_bias=False, keep_bf16=True)
+                x = bn_hardtanh(x, conv[1].batch_norm, conv[2], out_bf16=bf16, conv_bias=c1.bias,
+                                chan_sums=sums1)
             if bf16 and self.native_conv and native_conv.supported(c2, x):
                 y2, sums2 = native_conv.conv7x7c32(x, c2)
             else:

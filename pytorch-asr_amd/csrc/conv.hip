@@ -954,8 +954,46 @@ constexpr int C1_WGS = 1024;     // 4 workgroups per CU: the chunks' load latenc
 // MFMAs and stored to LDS behind them: the chunk loop then waits for HBM once per chunk at
 // most, not once per staging loop (first version: load -> LDS store loops with run-time
 // divisions, 13 us per chunk and workgroup for 17 KB of dy and 34 MFMAs).
-template <int DI, int WPT>
-__global__ __launch_bounds__(256) void conv1_wgrad_kernel(Conv1Params p) {
+//
+// BN: dy is the gradient reaching the OUTPUT of the BatchNorm + Hardtanh behind this
+// convolution, and the kernel forms the gradient of the convolution's output z itself, on the
+// way from the prefetch registers into LDS: the z pieces ride beside the dy pieces (same
+// offsets in the other tensor) and `stash` applies phase 2 of asr_bn_act_bwd_phase_f32
+// (bnact.hip, MODE 1 of bn_act_bwd_nhwc8_kernel) — the same operations in the same order, so
+// the MFMA operand has the bits the two-kernel path stores and reads back.  A thread's pieces
+// all hold channels 8 (tid & 3) .. + 7; the six constants of each of the 32 channels are worked
+// out once per workgroup into an LDS table (48 registers per thread otherwise: the <5, 2>
+// kernel has to stay within the 128 of four workgroups per CU).
+struct Conv1BnParams {
+    const __bf16 *z;              // the convolution's saved output, dy's layout
+    const float *shift;           // the convolution's bias (folded into the BatchNorm) or null
+    const float *gamma, *beta, *mean, *invstd;
+    const double *sums;           // [32][2]: sum of dyh, sum of dyh * xhat over n elements
+    double n;
+    float lo, hi;
+    int training;
+};
+
+// one bf16 pair (channels c, c + 1 of one pixel): ca / cb = { mean - shift, invstd, gamma, beta },
+// ka / kb = { k1, k2 }.  bnact.hip is compiled with the default contraction, under which the
+// compiler fuses MODE 1's  d - k1 - xh * k2  into  fma(-xh, k2, d - k1)  (the only contractible
+// product there); written out here so that it does not depend on this file's flags.
+__device__ __forceinline__ unsigned conv1_bn_bwd_pair(unsigned zw, unsigned dw, const f32x4 ca, const float2 ka,
+                                                      const f32x4 cb, const float2 kb, float lo, float hi) {
+#pragma clang fp contract(off)
+    const float z0 = __uint_as_float(zw << 16), z1 = __uint_as_float(zw & 0xffff0000u);
+    const float e0 = __uint_as_float(dw << 16), e1 = __uint_as_float(dw & 0xffff0000u);
+    const float xh0 = (z0 - ca[0]) * ca[1], xh1 = (z1 - cb[0]) * cb[1];
+    const float y0 = fmaf(xh0, ca[2], ca[3]), y1 = fmaf(xh1, cb[2], cb[3]);
+    const float d0 = (y0 > lo && y0 < hi) ? e0 : 0.f, d1 = (y1 > lo && y1 < hi) ? e1 : 0.f;
+    const float o0 = ca[2] * ca[1] * fmaf(-xh0, ka[1], d0 - ka[0]);
+    const float o1 = cb[2] * cb[1] * fmaf(-xh1, kb[1], d1 - kb[0]);
+    const __bf16 b0 = (__bf16)o0, b1 = (__bf16)o1;
+    return (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
+}
+
+template <int DI, int WPT, bool BN>
+__device__ __forceinline__ void conv1_wgrad_body(const Conv1Params &p, const Conv1BnParams &bn) {
     extern __shared__ char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -963,6 +1001,15 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(Conv1Params p) {
     const int nwin = (C1_ROWS + 8) * Fo;
     char *wimg = smem;                                                    // [C1_ROWS + 8][Fo] windows
     char *dimg = smem + (size_t)nwin * 16;                                // [npix] pixels x 80 B
+    float *ctab = reinterpret_cast<float *>(dimg + (size_t)npix * PIX);   // BN: [32 channels][8]
+    if (BN && tid < CH) {
+        ctab[8 * tid + 0] = bn.mean[tid] - (bn.shift ? bn.shift[tid] : 0.f);
+        ctab[8 * tid + 1] = bn.invstd[tid];
+        ctab[8 * tid + 2] = bn.gamma[tid];
+        ctab[8 * tid + 3] = bn.beta[tid];
+        ctab[8 * tid + 4] = bn.training ? (float)(bn.sums[2 * tid] / bn.n) : 0.f;
+        ctab[8 * tid + 5] = bn.training ? (float)(bn.sums[2 * tid + 1] / bn.n) : 0.f;
+    }                                       // (visible after the chunk loop's first barrier)
     f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -976,21 +1023,39 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(Conv1Params p) {
     const int chunks_per_utt = (p.To + C1_ROWS - 1) / C1_ROWS;
     const int nchunks = p.B * chunks_per_utt;
     const unsigned fmagic = (1u << 20) / (unsigned)Fo + 1u;      // i / Fo = (i * fmagic) >> 20 for i * Fo < 2^20
-    u32x4 dreg[DI];
+    u32x4 dreg[DI], zreg[BN ? DI : 1];
+    int dlim = 0;                           // BN: pixels of the prefetched chunk inside the tensor
     float2 wreg[WPT][4];
+    // BN: the thread index as a value the compiler cannot follow from one chunk to the next.
+    // With the plain `tid` it keeps every address that derives from it (64-bit offsets of the
+    // pieces, LDS addresses, window rows: some 50 registers) alive across the chunk loop; with
+    // the z pieces on top that is past the 128 registers of four workgroups per CU.  Recomputing
+    // them is a few integer instructions per chunk.
+    auto thread_index = [&]() {
+        int t = tid;
+        if (BN) asm volatile("" : "+v"(t));
+        return t;
+    };
     auto fetch = [&](int c) {
+        const int tix = thread_index();
         const int b = c / chunks_per_utt, t0 = (c - b * chunks_per_utt) * C1_ROWS;
-        const char *yb = reinterpret_cast<const char *>(p.y) + ((size_t)b * p.To + t0) * Fo * 64;
+        const size_t yoff = ((size_t)b * p.To + t0) * Fo * 64;
+        const char *yb = reinterpret_cast<const char *>(p.y) + yoff;
         const int rows_here = (p.To - t0) < C1_ROWS ? (p.To - t0) : C1_ROWS;
+        if (BN) dlim = rows_here * Fo;
 #pragma unroll
         for (int k = 0; k < DI; ++k) {
-            const int i = tid + 256 * k, pix = i >> 2;
+            const int i = tix + 256 * k, pix = i >> 2;
             dreg[k] = pix < rows_here * Fo ? *reinterpret_cast<const u32x4 *>(yb + (size_t)i * 16) : u32x4{0u, 0u, 0u, 0u};
+            if (BN) {
+                const char *zb = reinterpret_cast<const char *>(bn.z) + yoff;
+                zreg[k] = pix < rows_here * Fo ? *reinterpret_cast<const u32x4 *>(zb + (size_t)i * 16) : u32x4{0u, 0u, 0u, 0u};
+            }
         }
         const float *xb = p.x + (size_t)b * p.T * p.F;
 #pragma unroll
         for (int u = 0; u < WPT; ++u) {
-            const unsigned i = (unsigned)(tid + 256 * u);
+            const unsigned i = (unsigned)(tix + 256 * u);
             const unsigned row = (i * fmagic) >> 20, fo = i - row * (unsigned)Fo;
             const int t = t0 - 6 + (int)row;
             const bool ok = (int)i < nwin && t >= 0 && t < p.T;
@@ -1000,19 +1065,42 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(Conv1Params p) {
         }
     };
     auto stash = [&]() {
+        const int tix = thread_index();
+        auto stash_windows = [&]() {
+#pragma unroll
+            for (int u = 0; u < WPT; ++u) {
+                const int i = tix + 256 * u;
+                bf16x8 v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { v[2 * j] = (__bf16)wreg[u][j].x; v[2 * j + 1] = (__bf16)wreg[u][j].y; }
+                if (i < nwin) *reinterpret_cast<bf16x8 *>(wimg + (size_t)i * 16) = v;
+            }
+        };
+        if (BN) {
+            stash_windows();                // first: their registers are free for what follows
+            // dy -> dz in place, one channel pair (12 constants) of every piece at a time.  The
+            // empty asm statements pin that order: left to itself the compiler turns the loops
+            // inside out, pairs neighbouring channel pairs into packed instructions and holds
+            // all 48 constants of the thread's 8 channels, which does not fit.
+            const float *ct = ctab + 64 * (tix & 3);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 ca = *reinterpret_cast<const f32x4 *>(ct + 16 * j), cb = *reinterpret_cast<const f32x4 *>(ct + 16 * j + 8);
+                const float2 ka = *reinterpret_cast<const float2 *>(ct + 16 * j + 4), kb = *reinterpret_cast<const float2 *>(ct + 16 * j + 12);
+#pragma unroll
+                for (int k = 0; k < DI; ++k) {
+                    const unsigned o = conv1_bn_bwd_pair(zreg[k][j], dreg[k][j], ca, ka, cb, kb, bn.lo, bn.hi);
+                    dreg[k][j] = ((tix + 256 * k) >> 2) < dlim ? o : 0u;      // the zero pixels stay zero
+                    asm volatile("" : "+v"(dreg[k][j]) : : "memory");
+                }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < DI; ++k) {
-            const int i = tid + 256 * k, pix = i >> 2, part = i & 3;
+            const int i = tix + 256 * k, pix = i >> 2, part = i & 3;
             if (pix < npix) *reinterpret_cast<u32x4 *>(dimg + pix * PIX + part * 16) = dreg[k];
         }
-#pragma unroll
-        for (int u = 0; u < WPT; ++u) {
-            const int i = tid + 256 * u;
-            bf16x8 v;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { v[2 * j] = (__bf16)wreg[u][j].x; v[2 * j + 1] = (__bf16)wreg[u][j].y; }
-            if (i < nwin) *reinterpret_cast<bf16x8 *>(wimg + (size_t)i * 16) = v;
-        }
+        if (!BN) stash_windows();
     };
     if ((int)blockIdx.x < nchunks) fetch(blockIdx.x);
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
@@ -1051,6 +1139,17 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(Conv1Params p) {
     float *out = p.partial + (size_t)blockIdx.x * 2 * 1024;
     for (int e = tid; e < 2 * 1024; e += 256)
         out[e] = red[e] + red[2048 + e] + red[4096 + e] + red[6144 + e];
+}
+
+template <int DI, int WPT>
+__global__ __launch_bounds__(256) void conv1_wgrad_kernel(Conv1Params p) {
+    conv1_wgrad_body<DI, WPT, false>(p, Conv1BnParams{});
+}
+
+// <5, 2>: 122 registers, <8, 3>: 157, no scratch: the occupancies of the plain kernels (4, 3)
+template <int DI, int WPT>
+__global__ __launch_bounds__(256) void conv1_wgrad_bn_kernel(Conv1Params p, Conv1BnParams bn) {
+    conv1_wgrad_body<DI, WPT, true>(p, bn);
 }
 
 __global__ __launch_bounds__(1024) void conv1_wgrad_reduce_kernel(const float *partial, int nparts, float *dw) {
@@ -1527,9 +1626,17 @@ extern "C" int asr_conv1_7x7s2_fwd(const float *x, const float *w, int B, int T,
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
 }
 
-extern "C" int asr_conv1_7x7s2_wgrad(const float *x, const void *dy, int B, int T, int F,
-                                     float *dw, void *workspace, int64_t workspace_bytes,
-                                     void *stream) {
+// pieces of dy / windows per thread (256 threads): template sizes of the prefetch registers
+static void conv1_wgrad_sizes(int Fo, int *di, int *wpt) {
+    *di = (C1_ROWS * Fo * 4 + 255) / 256;
+    *wpt = ((C1_ROWS + 8) * Fo + 255) / 256;
+}
+
+// bn: null (dy is the gradient of the convolution's output) or the BatchNorm + Hardtanh
+// behind it, whose backward the kernel then applies to dy itself
+static int conv1_wgrad_launch(const float *x, const void *dy, int B, int T, int F, float *dw,
+                              void *workspace, int64_t workspace_bytes, const Conv1BnParams *bn,
+                              void *stream) {
     int To, Fo;
     const int rc = conv1_shapes(B, T, F, &To, &Fo);
     if (rc != ASR_OK) return rc;
@@ -1540,18 +1647,55 @@ extern "C" int asr_conv1_7x7s2_wgrad(const float *x, const void *dy, int B, int 
     p.x = x; p.wpack = nullptr; p.y = (__bf16 *)const_cast<void *>(dy);
     p.partial = (float *)((char *)workspace + 4 * 64 * 8 * 2);
     p.B = B; p.T = T; p.F = F; p.To = To; p.Fo = Fo;
-    size_t lds = (size_t)(C1_ROWS + 8) * Fo * 16 + (size_t)C1_ROWS * Fo * PIX;
+    size_t lds = (size_t)(C1_ROWS + 8) * Fo * 16 + (size_t)C1_ROWS * Fo * PIX + (bn ? CH * 8 * 4 : 0);
     if (lds < 4 * 2 * 1024 * 4) lds = 4 * 2 * 1024 * 4;            // the final four-wave sum
     if (lds > 64 * 1024) return ASR_EUNSUPPORTED;
     const int chunks = B * ((To + C1_ROWS - 1) / C1_ROWS);
     const int nwg = chunks < C1_WGS ? chunks : C1_WGS;
-    // pieces of dy / windows per thread (256 threads): template sizes of the prefetch registers
-    const int di = (C1_ROWS * Fo * 4 + 255) / 256, wpt = ((C1_ROWS + 8) * Fo + 255) / 256;
-    void (*kern)(Conv1Params) = di <= 5 && wpt <= 2 ? conv1_wgrad_kernel<5, 2>
-                              : (di <= 8 && wpt <= 3 ? conv1_wgrad_kernel<8, 3> : conv1_wgrad_kernel<16, 6>);
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, p);
+    int di, wpt;
+    conv1_wgrad_sizes(Fo, &di, &wpt);
+    if (bn) {
+        if (!asr_conv1_7x7s2_wgrad_bn_supported(F)) return ASR_EUNSUPPORTED;
+        void (*kern)(Conv1Params, Conv1BnParams) = di <= 5 && wpt <= 2 ? conv1_wgrad_bn_kernel<5, 2>
+                                                                         : conv1_wgrad_bn_kernel<8, 3>;
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, p, *bn);
+    } else {
+        void (*kern)(Conv1Params) = di <= 5 && wpt <= 2 ? conv1_wgrad_kernel<5, 2>
+                                  : (di <= 8 && wpt <= 3 ? conv1_wgrad_kernel<8, 3> : conv1_wgrad_kernel<16, 6>);
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, p);
+    }
     hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(2 * 1024 / 64), dim3(1024), 0, s, p.partial, nwg, dw);
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+}
+
+extern "C" int asr_conv1_7x7s2_wgrad(const float *x, const void *dy, int B, int T, int F,
+                                     float *dw, void *workspace, int64_t workspace_bytes,
+                                     void *stream) {
+    return conv1_wgrad_launch(x, dy, B, T, F, dw, workspace, workspace_bytes, nullptr, stream);
+}
+
+// widths whose fused kernel holds the z pieces beside the dy pieces without spilling: the
+// <16, 6> widths (Fo > 32: 64 + 64 + 48 prefetch registers) keep the two-kernel path
+extern "C" int asr_conv1_7x7s2_wgrad_bn_supported(int F) {
+    int To, Fo, di, wpt;
+    if (conv1_shapes(1, 1, F, &To, &Fo) != ASR_OK) return 0;
+    conv1_wgrad_sizes(Fo, &di, &wpt);
+    return di <= 8 && wpt <= 3;
+}
+
+extern "C" int asr_conv1_7x7s2_wgrad_bn(const float *x, const void *z, const void *dy, int B, int T, int F,
+                                        const float *conv_bias, const float *gamma, const float *beta,
+                                        const float *save_mean, const float *save_invstd,
+                                        int training, float lo, float hi, const void *bn_workspace,
+                                        double n_total, float *dw, void *workspace,
+                                        int64_t workspace_bytes, void *stream) {
+    if (!z || !gamma || !beta || !save_mean || !save_invstd || !bn_workspace || !(n_total >= 1.0))
+        return ASR_EINVAL;
+    Conv1BnParams bn;
+    bn.z = (const __bf16 *)z; bn.shift = conv_bias; bn.gamma = gamma; bn.beta = beta;
+    bn.mean = save_mean; bn.invstd = save_invstd; bn.sums = (const double *)bn_workspace;
+    bn.n = n_total; bn.lo = lo; bn.hi = hi; bn.training = training;
+    return conv1_wgrad_launch(x, dy, B, T, F, dw, workspace, workspace_bytes, &bn, stream);
 }
 
 
