@@ -1578,6 +1578,60 @@ int asr_lattice_lmrescore_sweep(
     double lattice_beam, int threads, float *out_alpha, float *out_beta, int32_t *out_keep, float *out_best,
     int32_t *out_status, void *stream);
 
+/*
+ * asr_lattice_seqtrain_f64: sequence-discriminative training statistics of every lattice of such a batch in
+ * one launch (csrc/lattice_train.hip): the denominator of lattice MMI / boosted MMI
+ * and the sMBR objective, from the LIVE log_probs.  LatticeBatch.seq_objective of att_speech/wfst_lattice.py is
+ * the numpy twin.  Additions: the ABI version stays 24.  The batch, b_begin / b_count and end(v) as for
+ * asr_lattice_posterior_f64; threads: 0 (= 64), 64, 128 or 256; acoustic_scale NaN: own_scale.  lat_lp and
+ * arc_olabel are part of the common batch arguments and are not read.
+ *
+ *   arc_ilabel [G] i32: the graph's input labels (class + 1; 0: epsilon); log_probs [T, B, C] f32;
+ *   ref [B, T] i32 the reference class of every frame (-1: none), or null: every accuracy 0;
+ *   criterion 0 (mmi) or 1 (smbr); boost >= 0, finite.
+ * Live score: an emitting arc a (il = arc_ilabel[lat_arc[a]] > 0) into time k = node_time[dst] has
+ *   s(a) = (double) log_probs[k-1, b, il-1], acc(a) = (ref[b, k-1] == il-1); an epsilon arc s = 0, acc = 0.
+ *   x(a) = fl(fl(fl(lm w) - fl(sc s)) + fl(boost acc)) in fp64, no contraction.
+ * fwd, bwd, log_z and gamma(a) = exp(fwd(src) - x + bwd(dst) - log_z) as in asr_lattice_posterior_f64 (max then
+ *   sum per node, one owner lane, stored order).  Expected accuracies in linear fp64 over the finite terms:
+ *   facc(v) = sum over in-arcs of exp(fwd(u) - x - fwd(v)) (facc(u) + acc(a)), facc(start) = 0;
+ *   bacc(u) = sum over out-arcs of exp(bwd(d) - x - bwd(u)) (bacc(d) + acc(a)), the stop term adds 0
+ *   (both computed as the weighted sum over exp(term - max) divided by the node's sum);
+ *   c_avg = bacc(start), c(a) = facc(src) + acc(a) + bacc(dst).
+ * mmi:  out_objective [B] = log_z, out_arc_grad [A] = gamma(a).
+ * smbr: out_objective [B] = c_avg, out_arc_grad [A] = gamma(a) (c(a) - c_avg).
+ *   No complete path (no nodes, log_z = -inf): objective -inf (mmi) / 0 (smbr), arc_grad 0.
+ * The emission index (built once per batch and [T, B, C]): em_arc [num_emitting] i32 the emitting arcs (batch
+ *   indices) sorted by (utterance, frame, class, arc); em_ptr [num_segments + 1] i32 the segments of equal
+ *   (utterance, frame, class); em_key [num_segments] i64 their offsets ((k-1) B + b) C + il-1 into out_occ,
+ *   ascending within an utterance; em_off [B + 1] i64 the segments of every utterance.
+ * out_occ [T, B, C] f32, zero on entry: entry em_key[s] = the float rounding of the fp64 sum of out_arc_grad
+ *   over segment s in ascending arc order, by one lane; other entries are not written.
+ *   d objective[b] / d log_probs[t, b, c] = sc out_occ[t, b, c].
+ * out_status [B] i32: 1 when an index read from the arrays was out of range, a level did not rise, an emitting
+ *   arc reads a frame or class outside [T, B, C], or the emission index does not list the utterance's emitting
+ *   arcs exactly once under their own keys (the utterance then has no result).  Nothing is read or written
+ *   out of bounds.
+ *   workspace: asr_lattice_seqtrain_workspace_bytes(nodes of the launch) = 32 bytes per node, rounded (fwd, bwd,
+ *   facc, bacc).  One workgroup per utterance, workgroup barriers only, no atomics on results: two runs, and
+ *   every workgroup size, give the same bits.
+ */
+int asr_lattice_seqtrain_supported(int64_t N, int64_t A, int64_t L);
+int64_t asr_lattice_seqtrain_workspace_bytes(int64_t num_nodes);
+int asr_lattice_seqtrain_f64(
+    int B, int b_begin, int b_count, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
+    const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
+    const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
+    const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
+    const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
+    const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
+    double acoustic_scale, double lm_scale, int64_t num_states, int64_t num_graph_arcs, const float *arc_weight,
+    const int32_t *arc_olabel, const float *final_cost, int start, int threads, const int32_t *arc_ilabel,
+    const float *log_probs, int T, int C, const int32_t *ref, int criterion, double boost, int64_t num_emitting,
+    int64_t num_segments, const int32_t *em_arc, const int32_t *em_ptr, const int64_t *em_key,
+    const int64_t *em_off, double *out_objective, double *out_arc_grad, float *out_occ, int32_t *out_status,
+    void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

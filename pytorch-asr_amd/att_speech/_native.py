@@ -114,6 +114,11 @@ _SIGNATURES = {
     'asr_lattice_oracle_i32': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
                                [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 2 + [_i] + [_vp] * 7 +
                                [_vp, _i64, _vp]),
+    'asr_lattice_seqtrain_supported': (_i, [_i64, _i64, _i64]),
+    'asr_lattice_seqtrain_workspace_bytes': (_i64, [_i64]),
+    'asr_lattice_seqtrain_f64': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
+                                 [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 2 + [_i, _i, _vp, _i,
+                                 ctypes.c_double, _i64, _i64] + [_vp] * 8 + [_vp, _i64, _vp]),
     'asr_lattice_lmrescore_supported': (_i, [_i64, _i64, _i64, _i]),
     'asr_lattice_lmrescore_workspace_bytes': (_i64, [_i64, _i]),
     'asr_lattice_lmrescore_expand': (_i, [_i] * 4 + [_i64] * 3 + [_vp] * 11 + [_i64, _vp, _i] + _LM_ARGS + [_vp] * 3 +

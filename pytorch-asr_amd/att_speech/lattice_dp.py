@@ -11,7 +11,9 @@ decodes it by minimum Bayes risk (the word sequence of the least expected word e
 per-word confidences and the confusion network) and `expected_errors` scores given sentences by that
 distance, all iterations in one launch of asr_lattice_mbr_f64 (section 4.23).  `oracle` finds the path nearest
 to a reference in word edit distance (lattice-oracle) in one launch of asr_lattice_oracle_i32 (section 4.25),
-and `depth` is lattice-depth.
+and `depth` is lattice-depth.  `seq_objective` is the training side: the lattice MMI / boosted MMI denominator and
+the sMBR objective from the live log_probs, with the occupancies as a [T, B, C] tensor, in one launch of
+asr_lattice_seqtrain_f64 (csrc/lattice_train.hip, section 4.26; att_speech.lattice_train wraps it in autograd).
 
 A batch on a GPU runs asr_lattice_bestpath_f64 / asr_lattice_posterior_f64 / asr_lattice_nbest_f64
 (csrc/lattice_dp.hip); a batch of CPU tensors, or ASR_LATTICE_DP_NATIVE=0 (ASR_LATTICE_NBEST_NATIVE=0
@@ -102,6 +104,7 @@ class DeviceLatticeBatch(object):
         self.num_classes = graph.max_ilabel if num_classes is None else int(num_classes)
         self.workspace_bytes = int(workspace_bytes)
         self._host = None
+        self._emission = {}                     # (T, C) -> the emission index of seq_objective
         self._build_levels()
 
     # ---- the level structure ------------------------------------------------------------
@@ -671,6 +674,113 @@ class DeviceLatticeBatch(object):
         if status.cpu().numpy().any():
             raise ValueError("asr_lattice_posterior_f64: the batch's index arrays are inconsistent")
         return res
+
+    # ---- sequence-discriminative training statistics ------------------------------------------
+    def _emission_index(self, T, C):
+        """The emitting arcs grouped by their entry of a [T, B, C] tensor, built once per batch and shape
+        with torch ops on the device: em_arc [E] int32 the emitting arcs by (utterance, frame, class, arc),
+        em_ptr [S+1] int32 the segments of equal (utterance, frame, class), em_key [S] int64 their offsets
+        ((k-1) B + b) C + class, em_off [B+1] int64 the segments of every utterance.  Raises ValueError when
+        an arc reads a class or a frame beyond [T, B, C]."""
+        hit = self._emission.get((T, C))
+        if hit is not None:
+            return hit
+        dev, B, A = self.device, self.num_utterances, self.num_arcs
+        i64 = dict(dtype=torch.int64, device=dev)
+        if A:
+            il = self.ilabel.long()
+            k = self.time.long()[self.dst_global]
+            arcs = torch.nonzero(il > 0).reshape(-1)
+            il, k, utt = il[arcs], k[arcs], self.arc_utt[arcs]
+            if int(arcs.numel()) and bool(((il > C) | (k > T) | (k < 1)).any()):
+                raise ValueError("seq_objective: the lattice has classes or frames beyond [T, B, C] = %s"
+                                 % ((T, B, C),))
+        else:
+            arcs = il = k = utt = torch.zeros(0, **i64)
+        E = int(arcs.numel())
+        flat = ((k - 1) * B + utt) * C + (il - 1)
+        order = torch.sort(utt * (T * B * C) + flat, stable=True)[1] if E else arcs    # arcs ascend already
+        flat, utt = flat[order], utt[order]
+        new = torch.ones(E, dtype=torch.bool, device=dev)
+        if E > 1:
+            new[1:] = (flat[1:] != flat[:-1]) | (utt[1:] != utt[:-1])
+        first = torch.nonzero(new).reshape(-1)
+        hit = dict(E=E, S=int(first.numel()), em_arc=arcs[order].int().contiguous(),
+                   em_ptr=torch.cat([first, torch.full((1,), E, **i64)]).int(),
+                   em_key=flat[first].contiguous(),
+                   em_off=torch.searchsorted(utt[first].contiguous(), torch.arange(B + 1, **i64)))
+        self._emission[(T, C)] = hit
+        return hit
+
+    def seq_objective(self, log_probs, ref=None, criterion='mmi', acoustic_scale=None, lm_scale=1.0, boost=0.0,
+                      workspace_bytes=None):
+        """The lattice MMI / boosted MMI denominator ('mmi': log Z and the arc posteriors) or the sMBR
+        objective ('smbr': the expected frame accuracy against `ref` and its derivative) of every lattice,
+        with the arc scores read from the LIVE log_probs [T, B, C] float32 instead of the lp stored at decode
+        time, so lattices made by a stale model can be reused.  LatticeBatch.seq_objective states the
+        semantics.  ref: [B, T] int32 classes per frame (CTCAlignment.frames, -1
+        padding) or None; boost >= 0 adds boost per correct frame to a path's cost (boosted MMI).
+
+        Returns (objective [B] f64, arc_grad [A] f64, occ [T, B, C] float32) on the batch's device;
+        d objective[b] / d log_probs[t, b, c] = acoustic_scale occ[t, b, c].  On a GPU one launch of
+        asr_lattice_seqtrain_f64 does the sweeps, the arcs and the scatter into occ (several launches when
+        workspace_bytes, default the batch's, does not hold 32 bytes per node at once; self.launches counts
+        them); two runs give the same bits.  A batch of CPU tensors and ASR_LATTICE_TRAIN_NATIVE=0 (read per
+        call) run the twin."""
+        if criterion not in ('mmi', 'smbr'):
+            raise ValueError("criterion must be 'mmi' or 'smbr', not %r" % (criterion,))
+        if not float(boost) >= 0.0 or float(boost) == INF:
+            raise ValueError("boost must be finite and >= 0")
+        B, dev, p = self.num_utterances, self.device, _native._p
+        if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3 or log_probs.size(1) != B:
+            raise ValueError("log_probs must be a [T, B = %d, C] tensor" % B)
+        if log_probs.device != dev:
+            raise ValueError("log_probs is on %s, the batch on %s" % (log_probs.device, dev))
+        T, _, C = log_probs.shape
+        if ref is not None:
+            ref = torch.as_tensor(ref)
+            if tuple(ref.shape) != (B, T) or ref.dtype.is_floating_point:
+                raise ValueError("ref must be an integer [B, T] = %s tensor, not %s" % ((B, T), tuple(ref.shape)))
+        native = dev.type == 'cuda' and os.environ.get('ASR_LATTICE_TRAIN_NATIVE', '1') != '0'
+        if not native:
+            out = self._host_batch().seq_objective(log_probs, ref, criterion, acoustic_scale, lm_scale, boost)
+            return tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in out)
+        if log_probs.dtype != torch.float32:
+            raise ValueError("log_probs must be float32 on the device")
+        smbr = criterion == 'smbr'
+        f64 = dict(dtype=torch.float64, device=dev)
+        objective = torch.full((B,), 0.0 if smbr else -INF, **f64)
+        arc_grad = torch.zeros(self.num_arcs, **f64)
+        occ = torch.zeros((T, B, C), dtype=torch.float32, device=dev)
+        self.launches = 0
+        if B == 0 or self.num_nodes == 0:
+            return objective, arc_grad, occ
+        L = _native.lib()
+        if not L.asr_lattice_seqtrain_supported(self.num_nodes, self.num_arcs, self.num_levels):
+            raise NotImplementedError("asr_lattice_seqtrain_f64: the batch is too large")
+        em = self._emission_index(int(T), int(C))
+        lp = log_probs.detach().contiguous()
+        ref_d = None if ref is None else ref.to(dev, torch.int32).contiguous()
+        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
+        chunks = self._utterance_chunks(32, budget)
+        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
+        nbytes = L.asr_lattice_seqtrain_workspace_bytes(biggest)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        head, tail = self._common_args()
+        il = self.graph.device_arrays(dev)['il']
+        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
+        for b0, b1 in chunks:
+            self._check(L.asr_lattice_seqtrain_f64(
+                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(il), p(lp), int(T), int(C), p(ref_d),
+                1 if smbr else 0, float(boost), em['E'], em['S'], p(em['em_arc']), p(em['em_ptr']),
+                p(em['em_key']), p(em['em_off']), p(objective), p(arc_grad), p(occ), p(status), p(ws), nbytes,
+                _native._stream()), 'asr_lattice_seqtrain_f64')
+            self.launches += 1
+        if status.cpu().numpy().any():
+            raise ValueError("asr_lattice_seqtrain_f64: the batch's index arrays are inconsistent, or an arc "
+                             "reads a frame or class beyond [T, B, C]")
+        return objective, arc_grad, occ
 
 
 def decode_lattice_device(log_probs, lens, graph, beam=16.0, lattice_beam=8.0, acoustic_scale=1.0,

@@ -686,6 +686,101 @@ class LatticeBatch(object):
                            part + bwd[self.dst] - za, -INF)
         return LatticePosteriors(self, log_z, arc, node, acoustic_scale, lm_scale)
 
+    # ---- sequence-discriminative training statistics -----------------------------------------------
+    def seq_objective(self, log_probs, ref=None, criterion='mmi', acoustic_scale=None, lm_scale=1.0, boost=0.0):
+        """The lattice MMI / boosted MMI denominator or the sMBR objective of every lattice, from the LIVE
+        scores: the numpy twin of asr_lattice_seqtrain_f64 (include/asr_amd.h states the semantics; DESIGN.md
+        section 4.26), fp64, level by level.
+
+        log_probs [T, B, C] float32 or float64 (array or tensor); ref [B, T] integer classes per frame
+        (CTCAlignment.frames; -1 never matches) or None (every accuracy 0).  An emitting arc into time k
+        scores s = log_probs[k - 1, b, ilabel - 1] (the stored lp is not read), acc = (ref[b, k - 1] ==
+        ilabel - 1), and costs x = lm_scale w - acoustic_scale s + boost acc.
+
+        Returns (objective [B] f64, arc_grad [arcs] f64, occ [T, B, C] float32):
+          'mmi'   log_z and the arc posteriors gamma;
+          'smbr'  the expected frame accuracy c_avg and gamma (c(a) - c_avg);
+        occ: arc_grad summed in fp64 per (frame, class) in ascending arc order, rounded once;
+        d objective[b] / d log_probs[t, b, c] = acoustic_scale occ[t, b, c].  An utterance without a
+        complete path has objective -inf ('mmi') or 0 ('smbr') and zero arc_grad and occ."""
+        if criterion not in ('mmi', 'smbr'):
+            raise ValueError("criterion must be 'mmi' or 'smbr', not %r" % (criterion,))
+        if not float(boost) >= 0.0 or float(boost) == INF:
+            raise ValueError("boost must be finite and >= 0")
+        lpr = log_probs.detach().cpu().numpy() if isinstance(log_probs, torch.Tensor) else np.asarray(log_probs)
+        if lpr.ndim != 3:
+            raise ValueError("log_probs must be [T, B, C]")
+        T, B, C = lpr.shape
+        if B != len(self.lattices):
+            raise ValueError("log_probs has %d utterances, the batch %d" % (B, len(self.lattices)))
+        smbr = criterion == 'smbr'
+        objective = np.full(B, 0.0 if smbr else -INF)
+        occ = np.zeros((T, B, C), np.float32)
+        A = len(self.arc) if B else 0
+        if ref is not None:
+            ref = ref.detach().cpu().numpy() if isinstance(ref, torch.Tensor) else np.asarray(ref)
+            if ref.shape != (B, T):
+                raise ValueError("ref must be [B, T] = %s, not %s" % ((B, T), tuple(ref.shape)))
+        if not B or not len(self.time):
+            return objective, np.zeros(A), occ
+        N = len(self.time)
+        il = self.graph.ilabel[self.arc].astype(np.int64)
+        k = self.time[self.dst]
+        a_utt = self.n_utt[self.src]
+        em = il > 0
+        if ((il[em] > C) | (k[em] > T) | (k[em] < 1)).any():
+            raise ValueError("seq_objective: the lattice has classes or frames beyond [T, B, C] = %s" % ((T, B, C),))
+        s = np.zeros(A)
+        acc = np.zeros(A)
+        s[em] = lpr[k[em] - 1, a_utt[em], il[em] - 1].astype(np.float64)
+        if ref is not None:
+            acc[em] = (ref[a_utt[em], k[em] - 1] == il[em] - 1).astype(np.float64)
+        sc = self.scale if acoustic_scale is None else float(acoustic_scale)
+        lm = float(lm_scale)
+        with np.errstate(invalid='ignore', over='ignore'):
+            x = lm * self.w - sc * s + float(boost) * acc
+            fwd = np.where(self.start, 0.0, -INF)
+            stop = np.where(self.end < INF, -(lm * np.where(self.end < INF, self.end, 0.0)), -INF)
+            bwd = stop.copy()
+            for lv, src, _, _ in self.levels:
+                ok = (fwd[src] > -INF) & (x[lv] < INF)
+                np.logaddexp.at(fwd, self.dst[lv][ok], fwd[src][ok] - x[lv][ok])
+            for lv, src, _, _ in reversed(self.levels):
+                d = self.dst[lv]
+                ok = (bwd[d] > -INF) & (x[lv] < INF)
+                np.logaddexp.at(bwd, src[ok], bwd[d][ok] - x[lv][ok])
+            # expected accuracies: a node's value is complete before its own arcs are taken
+            facc, bacc = np.zeros(N), np.zeros(N)
+            for lv, src, _, _ in self.levels:
+                d = self.dst[lv]
+                ok = (fwd[src] > -INF) & (x[lv] < INF) & (fwd[d] > -INF)
+                lv, src, d = lv[ok], src[ok], d[ok]
+                np.add.at(facc, d, np.exp(fwd[src] - x[lv] - fwd[d]) * (facc[src] + acc[lv]))
+            for lv, src, _, _ in reversed(self.levels):
+                d = self.dst[lv]
+                ok = (bwd[d] > -INF) & (x[lv] < INF) & (bwd[src] > -INF)
+                lv, src, d = lv[ok], src[ok], d[ok]
+                np.add.at(bacc, src, np.exp(bwd[d] - x[lv] - bwd[src]) * (bacc[d] + acc[lv]))
+            first = np.full(B, N, np.int64)
+            np.minimum.at(first, self.n_utt[self.start], np.nonzero(self.start)[0])
+            at = np.minimum(first, N - 1)
+            log_z = np.where(first < N, bwd[at], -INF)
+            have = log_z > -INF
+            c_avg = np.where(have, bacc[at], 0.0)
+            za = log_z[a_utt]
+            live = (fwd[self.src] > -INF) & (x < INF) & (bwd[self.dst] > -INF) & (za > -INF)
+            gamma = np.where(live, np.exp(np.where(live, fwd[self.src] - x + bwd[self.dst] - za, 0.0)), 0.0)
+        if smbr:
+            objective = c_avg
+            arc_grad = np.where(live, gamma * ((facc[self.src] + acc + bacc[self.dst]) - c_avg[a_utt]), 0.0)
+        else:
+            objective = log_z
+            arc_grad = gamma
+        flat = ((k[em] - 1) * B + a_utt[em]) * C + (il[em] - 1)
+        sums = np.zeros(T * B * C)
+        np.add.at(sums, flat, arc_grad[em])     # unbuffered: the arcs of an entry in ascending order
+        return objective, arc_grad, sums.reshape(T, B, C).astype(np.float32)
+
     # ---- the lattice oracle ---------------------------------------------------------------------
     def oracle(self, references, acoustic_scale=None, lm_scale=1.0):
         """The lattice oracle (Kaldi's lattice-oracle): per utterance the complete path whose words are
