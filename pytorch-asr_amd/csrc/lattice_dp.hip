@@ -28,68 +28,11 @@
 // All synchronise with workgroup barriers only.  Every node, arc, level and graph index read from
 // memory is range-checked before it is used (the tensors may come from a caller): a violation raises
 // the utterance's status word and ends its workgroup.  Every loop is bounded by the counts passed in.
+// The batch's header struct, those checks, the arithmetic of an arc and the host validation are csrc/lattice_batch.h's.
 #include "common.h"
-#include "../../include/asr_amd.h"
+#include "lattice_batch.h"
 
 namespace {
-
-constexpr double DINF = __builtin_huge_val();
-
-inline int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
-struct Lat {
-    int B;
-    int64_t N, A, L, G, S;                  // nodes, arcs, levels of the batch; graph arcs and states
-    const int64_t *node_off, *arc_off, *level_off;      // [B + 1]
-    const int32_t *time, *state, *level;    // [N]; level: index into level_ptr
-    const int32_t *src, *dst;               // [A] node indices of the utterance
-    const int64_t *arc;                     // [A] arc index in the graph
-    const float *lp;                        // [A]
-    const int32_t *level_ptr, *level_node;  // [L + 1], [N]: the nodes of a level (batch indices)
-    const int32_t *in_ptr, *in_arc;         // [N + 1], [A]: the in-arcs of a node (batch indices)
-    const int32_t *out_ptr;                 // [N + 1]: the out-arcs of node v are [out_ptr[v], out_ptr[v + 1])
-    const int32_t *frames, *reached;        // [B]
-    const double *own_scale;                // [B] the scale of the search
-    const float *w, *fin;                   // graph: [G], [S]
-    const int32_t *ol;                      // [G]
-    int start;
-    int b_begin, b_count;
-    int64_t n_begin;                        // node_off[b_begin]: the workspace starts there
-};
-
-struct Span {
-    int64_t n0, n1, a0, a1, l0, l1;
-    bool ok;
-};
-
-__device__ __forceinline__ Span span_of(const Lat &t, int b) {
-    Span s;
-    s.n0 = t.node_off[b], s.n1 = t.node_off[b + 1];
-    s.a0 = t.arc_off[b], s.a1 = t.arc_off[b + 1];
-    s.l0 = t.level_off[b], s.l1 = t.level_off[b + 1];
-    s.ok = t.n_begin <= s.n0 && s.n0 <= s.n1 && s.n1 <= t.N && 0 <= s.a0 && s.a0 <= s.a1 && s.a1 <= t.A &&
-           0 <= s.l0 && s.l0 <= s.l1 && s.l1 <= t.L;
-    return s;
-}
-
-// x = fl(fl(lm w) - fl(sc lp)); this file is compiled with -ffp-contract=off
-__device__ __forceinline__ double arc_cost(double lm, double sc, float w, float lp) {
-    const double a = lm * (double)w;
-    const double b = sc * (double)lp;
-    return a - b;
-}
-
-// the unscaled cost of stopping at node v (+inf: not an end node)
-__device__ __forceinline__ double end_cost(const Lat &t, int64_t v, int frames, int reached, bool &bad) {
-    if (t.time[v] != frames) return DINF;
-    if (!reached) return 0.0;
-    const int s = t.state[v];
-    if (s < 0 || s >= t.S) {
-        bad = true;
-        return DINF;
-    }
-    return (double)t.fin[s];
-}
 
 struct BestArgs {
     Lat t;
@@ -116,12 +59,7 @@ __global__ __launch_bounds__(NT) void lattice_bestpath_kernel(const BestArgs q) 
     const int64_t o = (int64_t)pr * t.B + b;
     const Span sp = span_of(t, b);
     const int64_t nlev = sp.l1 - sp.l0;
-    bool fail = !sp.ok;
-    if (!fail) {
-        const int32_t p0 = t.level_ptr[sp.l0], p1 = t.level_ptr[sp.l1];
-        fail = p0 != sp.n0 || p1 != sp.n1;      // the utterance's levels hold exactly its nodes
-    }
-    if (fail) {                                  // uniform: every lane read the same words
+    if (!sp.ok || !levels_cover(t, sp)) {       // uniform: every lane read the same words
         if (tid == 0) {
             q.out_cost[3 * o] = q.out_cost[3 * o + 1] = q.out_cost[3 * o + 2] = DINF;
             q.out_nwords[o] = 0;
@@ -129,20 +67,19 @@ __global__ __launch_bounds__(NT) void lattice_bestpath_kernel(const BestArgs q) 
         }
         return;
     }
-    double sc = q.ac_scale[pr];
-    if (sc != sc) sc = t.own_scale[b];
+    const double sc = scale_of(t, b, q.ac_scale[pr]);
     const double lm = q.lm_scale[pr];
     double *const cost = q.cost + (int64_t)pr * q.n_launch - t.n_begin;        // indexed by batch node
     int32_t *const bp = q.bp + (int64_t)pr * q.n_launch - t.n_begin;
     bool bad = false, nan = false, dead = false;
     for (int64_t l = sp.l0; l < sp.l1; ++l) {
         const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
-        if (e0 < sp.n0 || e0 > e1 || e1 > sp.n1) {
+        if (!level_range(e0, e1, sp.n0, sp.n1)) {
             bad = true;
         } else {
             for (int64_t e = e0 + tid; e < e1; e += NT) {
-                const int64_t v = t.level_node[e];
-                if (v < sp.n0 || v >= sp.n1 || t.level[v] != l) {
+                int64_t v, j0, j1;
+                if (!node_at(t, sp, e, l, v)) {
                     bad = true;
                     continue;
                 }
@@ -150,24 +87,13 @@ __global__ __launch_bounds__(NT) void lattice_bestpath_kernel(const BestArgs q) 
                 double c = is_start ? 0.0 : DINF;
                 int64_t best_g = INT64_MAX;
                 int32_t back = -1;
-                const int64_t j0 = t.in_ptr[v], j1 = t.in_ptr[v + 1];
-                if (j0 < sp.a0 || j0 > j1 || j1 > sp.a1) {
+                if (!in_arcs_of(t, sp, v, j0, j1)) {
                     bad = true;
                     continue;
                 }
                 for (int64_t j = j0; j < j1; ++j) {
-                    const int64_t a = t.in_arc[j];
-                    if (a < sp.a0 || a >= sp.a1) {
-                        bad = true;
-                        break;
-                    }
-                    const int64_t u = sp.n0 + t.src[a], g = t.arc[a];
-                    if (sp.n0 + t.dst[a] != v || u < sp.n0 || u >= sp.n1 || g < 0 || g >= t.G) {
-                        bad = true;
-                        break;
-                    }
-                    const int32_t lu = t.level[u];
-                    if (lu < sp.l0 || lu >= l) {           // the level must rise: cost[u] is final
+                    int64_t a, u, g;
+                    if (!in_arc_at(t, sp, j, v, l, a, u, g)) {
                         bad = true;
                         break;
                     }
@@ -223,13 +149,8 @@ __global__ __launch_bounds__(NT) void lattice_bestpath_kernel(const BestArgs q) 
         for (int64_t step = 0; step <= nlev; ++step) {      // a path has at most one arc per level
             const int32_t back = bp[cur];
             if (back < 0) break;
-            const int64_t a = sp.a0 + back;
-            if (a >= sp.a1) {
-                bad = true;
-                break;
-            }
-            const int64_t g = t.arc[a], u = sp.n0 + t.src[a];
-            if (g < 0 || g >= t.G || u < sp.n0 || u >= sp.n1 || t.level[u] >= t.level[cur]) {
+            int64_t a, u, g;
+            if (!back_arc_at(t, sp, back, cur, a, u, g)) {
                 bad = true;
                 break;
             }
@@ -267,11 +188,6 @@ struct PostArgs {
     int32_t *out_status;                    // [B]
 };
 
-__device__ __forceinline__ double lse_value(double m, double s) { return m == -DINF ? -DINF : m + log(s); }
-
-// a - x for log weights: -inf as soon as the path weight is zero
-__device__ __forceinline__ double log_times(double a, double x) { return (a == -DINF || x == DINF) ? -DINF : a - x; }
-
 template <int NT>
 __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q) {
     const Lat &t = q.t;
@@ -281,14 +197,11 @@ __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q)
     if (tid == 0) s_start = INT64_MAX;
     __syncthreads();
     const Span sp = span_of(t, b);
-    bool fail = !sp.ok;
-    if (!fail) fail = t.level_ptr[sp.l0] != sp.n0 || t.level_ptr[sp.l1] != sp.n1;
-    if (fail) {
+    if (!sp.ok || !levels_cover(t, sp)) {
         if (tid == 0) q.log_z[b] = -DINF, q.out_status[b] = 1;
         return;
     }
-    double sc = q.ac_scale;
-    if (sc != sc) sc = t.own_scale[b];
+    const double sc = scale_of(t, b, q.ac_scale);
     const double lm = q.lm_scale;
     double *const fwd = q.fwd - t.n_begin, *const bwd = q.bwd - t.n_begin;
     const int frames = t.frames[b], reached = t.reached[b];
@@ -296,19 +209,18 @@ __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q)
     // forward, levels upwards
     for (int64_t l = sp.l0; l < sp.l1; ++l) {
         const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
-        if (e0 < sp.n0 || e0 > e1 || e1 > sp.n1) {
+        if (!level_range(e0, e1, sp.n0, sp.n1)) {
             bad = true;
         } else {
             for (int64_t e = e0 + tid; e < e1; e += NT) {
-                const int64_t v = t.level_node[e];
-                if (v < sp.n0 || v >= sp.n1 || t.level[v] != l) {
+                int64_t v, j0, j1;
+                if (!node_at(t, sp, e, l, v)) {
                     bad = true;
                     continue;
                 }
                 const bool is_start = t.time[v] == 0 && t.state[v] == t.start;
                 if (is_start) atomicMin((unsigned long long *)&s_start, (unsigned long long)v);
-                const int64_t j0 = t.in_ptr[v], j1 = t.in_ptr[v + 1];
-                if (j0 < sp.a0 || j0 > j1 || j1 > sp.a1) {
+                if (!in_arcs_of(t, sp, v, j0, j1)) {
                     bad = true;
                     continue;
                 }
@@ -319,18 +231,8 @@ __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q)
                         s = is_start ? exp(0.0 - m) : 0.0;
                     }
                     for (int64_t j = j0; j < j1; ++j) {
-                        const int64_t a = t.in_arc[j];
-                        if (a < sp.a0 || a >= sp.a1) {
-                            bad = true;
-                            break;
-                        }
-                        const int64_t u = sp.n0 + t.src[a], g = t.arc[a];
-                        if (sp.n0 + t.dst[a] != v || u < sp.n0 || u >= sp.n1 || g < 0 || g >= t.G) {
-                            bad = true;
-                            break;
-                        }
-                        const int32_t lu = t.level[u];
-                        if (lu < sp.l0 || lu >= l) {
+                        int64_t a, u, g;
+                        if (!in_arc_at(t, sp, j, v, l, a, u, g)) {
                             bad = true;
                             break;
                         }
@@ -353,10 +255,10 @@ __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q)
             const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];     // checked in the forward
             for (int64_t e = e0 + tid; e < e1; e += NT) {
                 const int64_t v = t.level_node[e];
+                int64_t j0, j1;
                 const double en = end_cost(t, v, frames, reached, bad);
                 const double stop = en < DINF ? 0.0 - lm * en : -DINF;
-                const int64_t j0 = t.out_ptr[v], j1 = t.out_ptr[v + 1];
-                if (j0 < sp.a0 || j0 > j1 || j1 > sp.a1) {
+                if (!out_arcs_of(t, sp, v, j0, j1)) {
                     bad = true;
                     continue;
                 }
@@ -367,13 +269,8 @@ __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q)
                         s = stop != -DINF ? exp(stop - m) : 0.0;
                     }
                     for (int64_t a = j0; a < j1; ++a) {
-                        const int64_t d = sp.n0 + t.dst[a], g = t.arc[a];
-                        if (sp.n0 + t.src[a] != v || d < sp.n0 || d >= sp.n1 || g < 0 || g >= t.G) {
-                            bad = true;
-                            break;
-                        }
-                        const int32_t ld = t.level[d];
-                        if (ld <= l || ld >= sp.l1) {
+                        int64_t d, g;
+                        if (!out_arc_at(t, sp, a, v, l, d, g)) {
                             bad = true;
                             break;
                         }
@@ -400,8 +297,8 @@ __global__ __launch_bounds__(NT) void lattice_posterior_kernel(const PostArgs q)
     for (int64_t a = sp.a0 + tid; a < sp.a1; a += NT) {
         double r = -DINF;
         if (z != -DINF) {
-            const int64_t u = sp.n0 + t.src[a], d = sp.n0 + t.dst[a], g = t.arc[a];
-            if (u < sp.n0 || u >= sp.n1 || d < sp.n0 || d >= sp.n1 || g < 0 || g >= t.G) {
+            int64_t u, d, g;
+            if (!arc_at(t, sp, a, u, d, g)) {
                 bad = true;                     // an arc that no node's range covered
             } else {
                 const double part = log_times(fwd[u], arc_cost(lm, sc, t.w[g], t.lp[a]));
@@ -471,18 +368,6 @@ __device__ __forceinline__ NKey wave_min(NKey k) {
     return k;
 }
 
-// fl(lm end(v)) as Lattice._end_costs has it: 0 at the last time of a partial lattice
-__device__ __forceinline__ double scaled_end(const Lat &t, int64_t v, int frames, int reached, double lm, bool &bad) {
-    if (t.time[v] != frames) return DINF;
-    if (!reached) return 0.0;
-    const int s = t.state[v];
-    if (s < 0 || s >= t.S) {
-        bad = true;
-        return DINF;
-    }
-    return lm * (double)t.fin[s];
-}
-
 template <int NT>
 __global__ __launch_bounds__(NT) void lattice_nbest_kernel(const NbestArgs q) {
     const Lat &t = q.t;
@@ -494,14 +379,11 @@ __global__ __launch_bounds__(NT) void lattice_nbest_kernel(const NbestArgs q) {
     if (tid == 0) s_start = ~0ull;
     __syncthreads();
     const Span sp = span_of(t, b);
-    bool fail = !sp.ok;
-    if (!fail) fail = t.level_ptr[sp.l0] != sp.n0 || t.level_ptr[sp.l1] != sp.n1;
-    if (fail) {
+    if (!sp.ok || !levels_cover(t, sp)) {
         if (tid == 0) q.out_count[b] = 0, q.out_status[b] = 1;
         return;
     }
-    double sc = q.ac_scale;
-    if (sc != sc) sc = t.own_scale[b];
+    const double sc = scale_of(t, b, q.ac_scale);
     const double lm = q.lm_scale;
     const int frames = t.frames[b], reached = t.reached[b];
     const int64_t nlev = sp.l1 - sp.l0;
@@ -512,18 +394,17 @@ __global__ __launch_bounds__(NT) void lattice_nbest_kernel(const NbestArgs q) {
     bool bad = false, dead = false;
     for (int64_t l = sp.l1 - 1; l >= sp.l0; --l) {      // levels downwards: the lists above are final
         const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
-        if (e0 < sp.n0 || e0 > e1 || e1 > sp.n1) {
+        if (!level_range(e0, e1, sp.n0, sp.n1)) {
             bad = true;
         } else {
             for (int64_t e = e0 + wave; e < e1; e += NW) {      // everything here is uniform in the wave
-                const int64_t v = t.level_node[e];
-                if (v < sp.n0 || v >= sp.n1 || t.level[v] != l) {
+                int64_t v, j0, j1;
+                if (!node_at(t, sp, e, l, v)) {
                     bad = true;
                     continue;
                 }
                 if (lane == 0 && t.time[v] == 0 && t.state[v] == t.start) atomicMin(&s_start, (unsigned long long)v);
-                const int64_t j0 = t.out_ptr[v], j1 = t.out_ptr[v + 1];
-                if (j0 < sp.a0 || j0 > j1 || j1 > sp.a1) {
+                if (!out_arcs_of(t, sp, v, j0, j1)) {
                     bad = true;
                     continue;
                 }
@@ -541,21 +422,16 @@ __global__ __launch_bounds__(NT) void lattice_nbest_kernel(const NbestArgs q) {
                     int64_t dbase = 0;
                     int dcnt = 0, lo = 0;
                     if (has) {
-                        const int64_t d = sp.n0 + t.dst[a], g = t.arc[a];
-                        if (sp.n0 + t.src[a] != v || d < sp.n0 || d >= sp.n1 || g < 0 || g >= t.G) {
+                        int64_t d, g;
+                        if (!out_arc_at(t, sp, a, v, l, d, g)) {        // the level must rise: list(d) is final
                             bad = true, has = false;
                         } else {
-                            const int32_t ld = t.level[d];
-                            if (ld <= l || ld >= sp.l1) {       // the level must rise: list(d) is final
-                                bad = true, has = false;
-                            } else {
-                                x = arc_cost(lm, sc, t.w[g], t.lp[a]);
-                                olab = t.ol[g];
-                                dcnt = ecnt[d];
-                                dbase = d * n;
-                                if (dcnt < 0 || dcnt > n) bad = true, has = false;
-                                if (!(x < DINF)) has = false;   // +inf or NaN: no candidate survives
-                            }
+                            x = arc_cost(lm, sc, t.w[g], t.lp[a]);
+                            olab = t.ol[g];
+                            dcnt = ecnt[d];
+                            dbase = d * n;
+                            if (dcnt < 0 || dcnt > n) bad = true, has = false;
+                            if (!(x < DINF)) has = false;       // +inf or NaN: no candidate survives
                         }
                     }
                     const uint64_t arhi = (uint64_t)(a - sp.a0 + 1) << 32;
@@ -767,17 +643,14 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
     if (tid == 0) s_start = ~0ull, s_flags = 0, s_nw = 0, s_go = 0, s_count = 0, s_logz = -DINF;
     __syncthreads();
     const Span sp = span_of(t, b);
-    bool fail = !sp.ok;
-    if (!fail) fail = t.level_ptr[sp.l0] != sp.n0 || t.level_ptr[sp.l1] != sp.n1;
-    if (fail) {
+    if (!sp.ok || !levels_cover(t, sp)) {
         if (tid == 0) {
             q.out_nwords[b] = 0, q.out_risk[b] = DINF, q.out_iters[b] = 0, q.out_count[b] = 0;
             q.out_status[b] = 1;
         }
         return;
     }
-    double sc = q.ac_scale;
-    if (sc != sc) sc = t.own_scale[b];
+    const double sc = scale_of(t, b, q.ac_scale);
     const double lm = q.lm_scale;
     const int frames = t.frames[b], reached = t.reached[b];
     const int64_t nlev = sp.l1 - sp.l0;
@@ -788,26 +661,6 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
     int64_t *const gam = q.tab_gamma + (int64_t)b * q.cap;
     int64_t *const tau = q.tab_tau + (int64_t)b * q.cap;
     bool bad = false, dead = false;
-
-    // a node of level l and its in-arc range; an in-arc of it: all read from memory, all checked
-    auto node_at = [&](int64_t e, int64_t l, int64_t &v, int64_t &j0, int64_t &j1) -> bool {
-        v = t.level_node[e];
-        if (v < sp.n0 || v >= sp.n1 || t.level[v] != l) return false;
-        j0 = t.in_ptr[v], j1 = t.in_ptr[v + 1];
-        return j0 >= sp.a0 && j0 <= j1 && j1 <= sp.a1;
-    };
-    auto in_arc_at = [&](int64_t j, int64_t v, int64_t l, int64_t &a, int64_t &u, int64_t &g) -> bool {
-        a = t.in_arc[j];
-        if (a < sp.a0 || a >= sp.a1) return false;
-        u = sp.n0 + t.src[a], g = t.arc[a];
-        if (sp.n0 + t.dst[a] != v || u < sp.n0 || u >= sp.n1 || g < 0 || g >= t.G) return false;
-        const int32_t lu = t.level[u];
-        return lu >= sp.l0 && lu < l;            // the level must rise: u is final
-    };
-    auto levels_ok = [&](int64_t l, int64_t &e0, int64_t &e1) -> bool {
-        e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
-        return e0 >= sp.n0 && e0 <= e1 && e1 <= sp.n1;
-    };
 
     for (int64_t v = sp.n0 + tid; v < sp.n1; v += NT)
         if (t.time[v] == 0 && t.state[v] == t.start) atomicMin(&s_start, (unsigned long long)v);
@@ -831,13 +684,13 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
         auto bp = [&](int64_t v) -> int32_t & { return *(int32_t *)(beta + v * C); };
         bool nan = false;
         for (int64_t l = sp.l0; l < sp.l1; ++l) {
-            int64_t e0, e1;
-            if (!levels_ok(l, e0, e1)) {
+            const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
+            if (!level_range(e0, e1, sp.n0, sp.n1)) {
                 bad = true;
             } else {
                 for (int64_t e = e0 + tid; e < e1; e += NT) {
                     int64_t v, j0, j1;
-                    if (!node_at(e, l, v, j0, j1)) {
+                    if (!node_at(t, sp, e, l, v) || !in_arcs_of(t, sp, v, j0, j1)) {
                         bad = true;
                         continue;
                     }
@@ -847,7 +700,7 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
                     int32_t back = -1;
                     for (int64_t j = j0; j < j1; ++j) {
                         int64_t a, u, g;
-                        if (!in_arc_at(j, v, l, a, u, g)) {
+                        if (!in_arc_at(t, sp, j, v, l, a, u, g)) {
                             bad = true;
                             break;
                         }
@@ -895,13 +748,8 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
             for (int64_t step = 0; step <= nlev && mi >= 0; ++step) {   // a path has at most one arc per level
                 const int32_t back = bp(cur);
                 if (back < 0) break;
-                const int64_t a = sp.a0 + back;
-                if (a >= sp.a1) {
-                    flags |= 1;
-                    break;
-                }
-                const int64_t g = t.arc[a], u = sp.n0 + t.src[a];
-                if (g < 0 || g >= t.G || u < sp.n0 || u >= sp.n1 || t.level[u] >= t.level[cur]) {
+                int64_t a, u, g;
+                if (!back_arc_at(t, sp, back, cur, a, u, g)) {
                     flags |= 1;
                     break;
                 }
@@ -932,13 +780,13 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
     const bool own = !q.arc_cond || !q.end_cond;
     if (own && !none && !dead && !(s_flags & 4)) {
         for (int64_t l = sp.l0; l < sp.l1; ++l) {
-            int64_t e0, e1;
-            if (!levels_ok(l, e0, e1)) {
+            const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
+            if (!level_range(e0, e1, sp.n0, sp.n1)) {
                 bad = true;
             } else {
                 for (int64_t e = e0 + tid; e < e1; e += NT) {
                     int64_t v, j0, j1;
-                    if (!node_at(e, l, v, j0, j1)) {
+                    if (!node_at(t, sp, e, l, v) || !in_arcs_of(t, sp, v, j0, j1)) {
                         bad = true;
                         continue;
                     }
@@ -951,7 +799,7 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
                         }
                         for (int64_t j = j0; j < j1; ++j) {
                             int64_t a, u, g;
-                            if (!in_arc_at(j, v, l, a, u, g)) {
+                            if (!in_arc_at(t, sp, j, v, l, a, u, g)) {
                                 bad = true;
                                 break;
                             }
@@ -1145,13 +993,13 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
 
         // forward, levels upwards: a wave owns a node and takes its in-arcs in turn
         for (int64_t l = sp.l0; l < sp.l1; ++l) {
-            int64_t e0, e1;
-            if (!levels_ok(l, e0, e1)) {
+            const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
+            if (!level_range(e0, e1, sp.n0, sp.n1)) {
                 bad = true;
             } else {
                 for (int64_t e = e0 + wave; e < e1; e += NW) {
                     int64_t v, j0, j1;
-                    if (!node_at(e, l, v, j0, j1)) {
+                    if (!node_at(t, sp, e, l, v) || !in_arcs_of(t, sp, v, j0, j1)) {
                         bad = true;
                         continue;
                     }
@@ -1164,7 +1012,7 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
                     for (int k = lane; k <= S; k += 64) acc[k] = 0;
                     for (int64_t j = j0; j < j1; ++j) {
                         int64_t a, u, g;
-                        if (!in_arc_at(j, v, l, a, u, g)) {
+                        if (!in_arc_at(t, sp, j, v, l, a, u, g)) {
                             bad = true;
                             break;
                         }
@@ -1203,11 +1051,10 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
         risk = s_ae[S];
         // backward, levels downwards
         for (int64_t l = sp.l1 - 1; l >= sp.l0; --l) {
-            int64_t e0, e1;
-            levels_ok(l, e0, e1);               // checked in the forward
+            const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];     // checked in the forward
             for (int64_t e = e0 + wave; e < e1; e += NW) {
                 int64_t v, j0, j1;
-                if (!node_at(e, l, v, j0, j1)) {
+                if (!node_at(t, sp, e, l, v) || !in_arcs_of(t, sp, v, j0, j1)) {
                     bad = true;
                     continue;
                 }
@@ -1218,7 +1065,7 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
                 const int tv = t.time[v];
                 for (int64_t j = j0; j < j1; ++j) {
                     int64_t a, u, g;
-                    if (!in_arc_at(j, v, l, a, u, g)) {
+                    if (!in_arc_at(t, sp, j, v, l, a, u, g)) {
                         bad = true;
                         break;
                     }
@@ -1305,50 +1152,6 @@ __global__ __launch_bounds__(NT) void lattice_mbr_kernel(const MbrArgs q) {
     }
 }
 
-bool sizes_ok(int64_t N, int64_t A, int64_t L) {
-    const int64_t lim = ((int64_t)1 << 31) - 1;
-    return N >= 0 && A >= 0 && L >= 0 && N < lim && A < lim && L < lim;
-}
-
-// the host copies of the offsets: [B + 1], from 0 to total, never decreasing
-bool offsets_ok(const int64_t *h, int B, int64_t total) {
-    if (!h || h[0] != 0 || h[B] != total) return false;
-    for (int b = 0; b < B; ++b)
-        if (h[b + 1] < h[b]) return false;
-    return true;
-}
-
-int fill(Lat &t, int B, int b_begin, int b_count, int64_t N, int64_t A, int64_t L, const int64_t *h_node_off,
-         const int64_t *h_arc_off, const int64_t *h_level_off, const int64_t *node_off, const int64_t *arc_off,
-         const int64_t *level_off, const int32_t *node_time, const int32_t *node_state, const int32_t *node_level,
-         const int32_t *lat_src, const int32_t *lat_dst, const int64_t *lat_arc, const float *lat_lp,
-         const int32_t *level_ptr, const int32_t *level_node, const int32_t *in_ptr, const int32_t *in_arc,
-         const int32_t *out_ptr, const int32_t *num_frames, const int32_t *reached_final, const double *own_scale,
-         int64_t S, int64_t G, const float *arc_weight, const int32_t *arc_olabel, const float *final_cost,
-         int start) {
-    if (B < 0 || b_begin < 0 || b_count < 0 || (int64_t)b_begin + b_count > B) return ASR_EINVAL;
-    if (N < 0 || A < 0 || L < 0 || S < 1 || G < 0 || start < 0 || start >= S) return ASR_EINVAL;
-    if (!sizes_ok(N, A, L)) return ASR_EUNSUPPORTED;
-    if (!offsets_ok(h_node_off, B, N) || !offsets_ok(h_arc_off, B, A) || !offsets_ok(h_level_off, B, L))
-        return ASR_EINVAL;
-    for (int b = 0; b < B; ++b) {               // a level holds a node; arcs need two nodes on two levels
-        const int64_t n = h_node_off[b + 1] - h_node_off[b], l = h_level_off[b + 1] - h_level_off[b];
-        if (l > n || (n > 0 && l < 1) || (h_arc_off[b + 1] > h_arc_off[b] && l < 2)) return ASR_EINVAL;
-    }
-    if (!node_off || !arc_off || !level_off || !level_ptr || !in_ptr || !out_ptr || !num_frames || !reached_final ||
-        !own_scale || !final_cost)
-        return ASR_EINVAL;
-    if (N > 0 && (!node_time || !node_state || !node_level || !level_node)) return ASR_EINVAL;
-    if (A > 0 && (!lat_src || !lat_dst || !lat_arc || !lat_lp || !in_arc || !arc_weight || !arc_olabel))
-        return ASR_EINVAL;
-    t = Lat{B, N, A, L, G, S, node_off, arc_off, level_off, node_time, node_state, node_level, lat_src, lat_dst,
-            lat_arc, lat_lp, level_ptr, level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final, own_scale,
-            arc_weight, final_cost, arc_olabel, start, b_begin, b_count, h_node_off[b_begin]};
-    return ASR_OK;
-}
-
-bool threads_ok(int threads) { return threads == 0 || threads == 64 || threads == 128 || threads == 256; }
-
 }  // namespace
 
 extern "C" int asr_lattice_bestpath_supported(int64_t N, int64_t A, int64_t L) { return sizes_ok(N, A, L) ? 1 : 0; }
@@ -1377,10 +1180,10 @@ extern "C" int asr_lattice_bestpath_f64(
     double *out_cost, int32_t *out_num_words, int32_t *out_words, int32_t *out_status, void *workspace,
     int64_t workspace_bytes, void *stream) {
     BestArgs q;
-    const int rc = fill(q.t, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off, node_off, arc_off,
-                        level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc, lat_lp, level_ptr,
-                        level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final, own_scale, num_states,
-                        num_graph_arcs, arc_weight, arc_olabel, final_cost, start);
+    const int rc = fill_lat(q.t, LAT_LP | LAT_OLABEL, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off,
+                            node_off, arc_off, level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc,
+                            lat_lp, level_ptr, level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final,
+                            own_scale, num_states, num_graph_arcs, arc_weight, arc_olabel, nullptr, final_cost, start);
     if (rc != ASR_OK) return rc;
     if (num_pairs < 0 || !threads_ok(threads)) return ASR_EINVAL;
     if (b_count == 0 || num_pairs == 0) return ASR_OK;
@@ -1400,13 +1203,8 @@ extern "C" int asr_lattice_bestpath_f64(
     q.out_nwords = out_num_words;
     q.out_words = out_words;
     q.out_status = out_status;
-    const dim3 grid((unsigned)((int64_t)b_count * num_pairs));
-    switch (threads) {
-    case 256: hipLaunchKernelGGL(lattice_bestpath_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, q); break;
-    case 128: hipLaunchKernelGGL(lattice_bestpath_kernel<128>, grid, dim3(128), 0, (hipStream_t)stream, q); break;
-    default: hipLaunchKernelGGL(lattice_bestpath_kernel<64>, grid, dim3(64), 0, (hipStream_t)stream, q); break;
-    }
-    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+    return launch_by_threads(threads, 64, (int64_t)b_count * num_pairs, stream, q, lattice_bestpath_kernel<64>,
+                             lattice_bestpath_kernel<128>, lattice_bestpath_kernel<256>);
 }
 
 extern "C" int asr_lattice_posterior_f64(
@@ -1421,10 +1219,10 @@ extern "C" int asr_lattice_posterior_f64(
     double *out_arc_log_post, double *out_node_log_post, int32_t *out_status, void *workspace,
     int64_t workspace_bytes, void *stream) {
     PostArgs q;
-    const int rc = fill(q.t, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off, node_off, arc_off,
-                        level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc, lat_lp, level_ptr,
-                        level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final, own_scale, num_states,
-                        num_graph_arcs, arc_weight, arc_olabel, final_cost, start);
+    const int rc = fill_lat(q.t, LAT_LP | LAT_OLABEL, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off,
+                            node_off, arc_off, level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc,
+                            lat_lp, level_ptr, level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final,
+                            own_scale, num_states, num_graph_arcs, arc_weight, arc_olabel, nullptr, final_cost, start);
     if (rc != ASR_OK) return rc;
     if (!threads_ok(threads)) return ASR_EINVAL;
     if (b_count == 0) return ASR_OK;
@@ -1440,13 +1238,8 @@ extern "C" int asr_lattice_posterior_f64(
     q.arc_post = out_arc_log_post;
     q.node_post = out_node_log_post;
     q.out_status = out_status;
-    const dim3 grid((unsigned)b_count);
-    switch (threads) {
-    case 256: hipLaunchKernelGGL(lattice_posterior_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, q); break;
-    case 128: hipLaunchKernelGGL(lattice_posterior_kernel<128>, grid, dim3(128), 0, (hipStream_t)stream, q); break;
-    default: hipLaunchKernelGGL(lattice_posterior_kernel<64>, grid, dim3(64), 0, (hipStream_t)stream, q); break;
-    }
-    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+    return launch_by_threads(threads, 64, b_count, stream, q, lattice_posterior_kernel<64>,
+                             lattice_posterior_kernel<128>, lattice_posterior_kernel<256>);
 }
 
 extern "C" int asr_lattice_nbest_supported(int64_t N, int64_t A, int64_t L, int n) {
@@ -1471,10 +1264,10 @@ extern "C" int asr_lattice_nbest_f64(
     double *out_cost, int32_t *out_num_words, int32_t *out_words, int32_t *out_status, void *workspace,
     int64_t workspace_bytes, void *stream) {
     NbestArgs q;
-    const int rc = fill(q.t, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off, node_off, arc_off,
-                        level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc, lat_lp, level_ptr,
-                        level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final, own_scale, num_states,
-                        num_graph_arcs, arc_weight, arc_olabel, final_cost, start);
+    const int rc = fill_lat(q.t, LAT_LP | LAT_OLABEL, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off,
+                            node_off, arc_off, level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc,
+                            lat_lp, level_ptr, level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final,
+                            own_scale, num_states, num_graph_arcs, arc_weight, arc_olabel, nullptr, final_cost, start);
     if (rc != ASR_OK) return rc;
     if (n < 1 || !threads_ok(threads)) return ASR_EINVAL;
     if (n > NBEST_MAX) return ASR_EUNSUPPORTED;
@@ -1499,13 +1292,9 @@ extern "C" int asr_lattice_nbest_f64(
     q.out_nwords = out_num_words;
     q.out_words = out_words;
     q.out_status = out_status;
-    const dim3 grid((unsigned)b_count);
-    switch (threads) {                          // 0: four waves, four nodes of a level at a time (section 4.22)
-    case 64: hipLaunchKernelGGL(lattice_nbest_kernel<64>, grid, dim3(64), 0, (hipStream_t)stream, q); break;
-    case 128: hipLaunchKernelGGL(lattice_nbest_kernel<128>, grid, dim3(128), 0, (hipStream_t)stream, q); break;
-    default: hipLaunchKernelGGL(lattice_nbest_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, q); break;
-    }
-    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+    // threads 0: four waves, four nodes of a level at a time (section 4.22)
+    return launch_by_threads(threads, 256, b_count, stream, q, lattice_nbest_kernel<64>, lattice_nbest_kernel<128>,
+                             lattice_nbest_kernel<256>);
 }
 
 extern "C" int asr_lattice_mbr_supported(int64_t N, int64_t A, int64_t L, int max_words) {
@@ -1533,10 +1322,10 @@ extern "C" int asr_lattice_mbr_f64(
     int32_t *out_sausage_count, int64_t *out_sausage_key, int64_t *out_sausage_gamma, int64_t *out_sausage_tau,
     void *workspace, int64_t workspace_bytes, void *stream) {
     MbrArgs q;
-    const int rc = fill(q.t, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off, node_off, arc_off,
-                        level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc, lat_lp, level_ptr,
-                        level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final, own_scale, num_states,
-                        num_graph_arcs, arc_weight, arc_olabel, final_cost, start);
+    const int rc = fill_lat(q.t, LAT_LP | LAT_OLABEL, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off,
+                            node_off, arc_off, level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc,
+                            lat_lp, level_ptr, level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final,
+                            own_scale, num_states, num_graph_arcs, arc_weight, arc_olabel, nullptr, final_cost, start);
     if (rc != ASR_OK) return rc;
     if (max_words < 1 || max_iterations < 0 || sausage_cap < 1 || !threads_ok(threads)) return ASR_EINVAL;
     if (max_words > MBR_MAX_WORDS || sausage_cap >= ((int64_t)1 << 31)) return ASR_EUNSUPPORTED;
@@ -1574,11 +1363,7 @@ extern "C" int asr_lattice_mbr_f64(
     q.tab_key = out_sausage_key;
     q.tab_gamma = out_sausage_gamma;
     q.tab_tau = out_sausage_tau;
-    const dim3 grid((unsigned)b_count);
-    switch (threads) {                          // 0: four waves, four nodes of a level at a time
-    case 64: hipLaunchKernelGGL(lattice_mbr_kernel<64>, grid, dim3(64), 0, (hipStream_t)stream, q); break;
-    case 128: hipLaunchKernelGGL(lattice_mbr_kernel<128>, grid, dim3(128), 0, (hipStream_t)stream, q); break;
-    default: hipLaunchKernelGGL(lattice_mbr_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, q); break;
-    }
-    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+    // threads 0: four waves, four nodes of a level at a time
+    return launch_by_threads(threads, 256, b_count, stream, q, lattice_mbr_kernel<64>, lattice_mbr_kernel<128>,
+                             lattice_mbr_kernel<256>);
 }

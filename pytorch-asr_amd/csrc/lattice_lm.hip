@@ -17,22 +17,14 @@
 // All synchronise with workgroup barriers only.  Every index read from memory is range-checked before it is
 // used; a violation raises the utterance's status word.  Every loop is bounded by the counts passed in.
 #include "common.h"
-#include "../../include/asr_amd.h"
+#include "lattice_batch.h"                      // DINF, up16, sizes_ok; the argument structs here are this file's own
 
 namespace {
 
-constexpr double DINF = __builtin_huge_val();
 constexpr float FINF = __builtin_huge_valf();
 constexpr int MAX_STATES = ASR_LATTICE_LMRESCORE_MAX_STATES;
 constexpr int NT = 256;
 constexpr int NW = NT / ASR_WAVE;
-
-inline int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
-bool sizes_ok(int64_t N, int64_t A, int64_t L) {
-    const int64_t top = ((int64_t)1 << 31) - 1;
-    return N >= 0 && A >= 0 && L >= 0 && N < top && A < top && L < top;
-}
 
 struct Lm {
     int64_t Q, LA;                          // states, non-epsilon arcs

@@ -5,81 +5,24 @@
 // frame every reference word was aligned to.  LatticeBatch.oracle of att_speech/wfst_lattice.py is the numpy
 // twin; the distances are int32, so both agree with ==.
 //
-// The batch is the one of csrc/lattice_dp.hip (nodes by (utterance, time, state), arcs by (utterance, source
-// node, graph arc), the (time, epsilon rank) levels, the in-arcs of every node), and so is the shape of the
-// kernel: one workgroup per utterance, persistent over its levels; a wave owns a node of a level and takes its
-// in-arcs in turn; its lanes run over the reference positions q = 0 .. R in rounds of 64.  The deletion chain
-// D(v, q) = min(D0(v, q), D(v, q - 1) + 1) is q + the running minimum of D0(v, i) - i: a wave-level prefix
-// minimum with a carry between the rounds.  The rows D(v, .) stay in the workspace; one wave walks them back
-// from the end node, a lane per in-arc, the first arc that attains D(v, q) found by ballot.
+// The batch, its checked traversal and the host validation are csrc/lattice_batch.h's (nodes by (utterance, time,
+// state), arcs by (utterance, source node, graph arc), the (time, epsilon rank) levels, the in-arcs of every
+// node); the shape of the kernel is that of csrc/lattice_dp.hip's: one workgroup per utterance, persistent over
+// its levels; a wave owns a node of a level and takes its in-arcs in turn; its lanes run over the reference
+// positions q = 0 .. R in rounds of 64.  The deletion chain D(v, q) = min(D0(v, q), D(v, q - 1) + 1) is q + the
+// running minimum of D0(v, i) - i: a wave-level prefix minimum with a carry between the rounds.  The rows D(v, .)
+// stay in the workspace; one wave walks them back from the end node, a lane per in-arc, the first arc that
+// attains D(v, q) found by ballot.
 //
 // Workgroup barriers only.  Every node, arc, level and graph index read from memory is range-checked before
 // it is used: a violation raises the utterance's status word.  Every loop is bounded by the counts passed in.
 #include "common.h"
-#include "../../include/asr_amd.h"
+#include "lattice_batch.h"
 
 namespace {
 
-constexpr double DINF = __builtin_huge_val();
 constexpr int ORACLE_MAX_WORDS = ASR_LATTICE_ORACLE_MAX_WORDS;
 constexpr int32_t UNREACHABLE = 1 << 30;        // U: no path; every sum is clamped to it
-
-inline int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
-// the batch, as csrc/lattice_dp.hip lays it out
-struct Lat {
-    int B;
-    int64_t N, A, L, G, S;                  // nodes, arcs, levels of the batch; graph arcs and states
-    const int64_t *node_off, *arc_off, *level_off;      // [B + 1]
-    const int32_t *time, *state, *level;    // [N]; level: index into level_ptr
-    const int32_t *src, *dst;               // [A] node indices of the utterance
-    const int64_t *arc;                     // [A] arc index in the graph
-    const float *lp;                        // [A]
-    const int32_t *level_ptr, *level_node;  // [L + 1], [N]: the nodes of a level (batch indices)
-    const int32_t *in_ptr, *in_arc;         // [N + 1], [A]: the in-arcs of a node (batch indices)
-    const int32_t *frames, *reached;        // [B]
-    const double *own_scale;                // [B] the scale of the search
-    const float *w, *fin;                   // graph: [G], [S]
-    const int32_t *ol;                      // [G]
-    int start;
-    int b_begin, b_count;
-    int64_t n_begin, n_end;                 // node_off[b_begin], node_off[b_begin + b_count]: the workspace's nodes
-};
-
-struct Span {
-    int64_t n0, n1, a0, a1, l0, l1;
-    bool ok;
-};
-
-__device__ __forceinline__ Span span_of(const Lat &t, int b) {
-    Span s;
-    s.n0 = t.node_off[b], s.n1 = t.node_off[b + 1];
-    s.a0 = t.arc_off[b], s.a1 = t.arc_off[b + 1];
-    s.l0 = t.level_off[b], s.l1 = t.level_off[b + 1];
-    s.ok = t.n_begin <= s.n0 && s.n0 <= s.n1 && s.n1 <= t.n_end && s.n1 <= t.N && 0 <= s.a0 && s.a0 <= s.a1 &&
-           s.a1 <= t.A && 0 <= s.l0 && s.l0 <= s.l1 && s.l1 <= t.L;
-    return s;
-}
-
-// x = fl(fl(lm w) - fl(sc lp)); this file is compiled with -ffp-contract=off
-__device__ __forceinline__ double arc_cost(double lm, double sc, float w, float lp) {
-    const double a = lm * (double)w;
-    const double b = sc * (double)lp;
-    return a - b;
-}
-
-// fl(lm end(v)): 0 at the last time of a partial lattice; +inf: not an end node
-__device__ __forceinline__ double scaled_end(const Lat &t, int64_t v, int frames, int reached, double lm, bool &bad) {
-    if (t.time[v] != frames) return DINF;
-    if (!reached) return 0.0;
-    const int s = t.state[v];
-    if (s < 0 || s >= t.S) {
-        bad = true;
-        return DINF;
-    }
-    const float f = t.fin[s];
-    return f < __builtin_huge_valf() ? lm * (double)f : DINF;
-}
 
 struct OracleArgs {
     Lat t;
@@ -120,39 +63,20 @@ __global__ __launch_bounds__(NT) void lattice_oracle_kernel(const OracleArgs q) 
     __syncthreads();
     const Span sp = span_of(t, b);
     const int R = q.ref_nwords[b];
-    bool fail = !sp.ok || R < 0 || R > W;
-    if (!fail) fail = t.level_ptr[sp.l0] != sp.n0 || t.level_ptr[sp.l1] != sp.n1;
-    if (fail) {                                 // uniform: every lane read the same words
+    if (!sp.ok || R < 0 || R > W || !levels_cover(t, sp)) {     // uniform: every lane read the same words
         if (tid == 0) {
             q.out_errors[b] = -1, q.out_nwords[b] = 0, q.out_cost[b] = DINF, q.out_status[b] = 1;
             for (int k = 0; k < 4; ++k) q.out_counts[4 * (int64_t)b + k] = 0;
         }
         return;
     }
-    double sc = q.ac_scale;
-    if (sc != sc) sc = t.own_scale[b];
+    const double sc = scale_of(t, b, q.ac_scale);
     const double lm = q.lm_scale;
     const int frames = t.frames[b], reached = t.reached[b];
     const int64_t nlev = sp.l1 - sp.l0;
     int32_t *const D = q.D - t.n_begin * C;     // indexed by batch node * C + position
     const int32_t *const ref = q.ref_words + (int64_t)b * W;
     bool bad = false, dead = false;
-
-    // a node of level l and its in-arc range; an in-arc of it: all read from memory, all checked
-    auto node_at = [&](int64_t e, int64_t l, int64_t &v, int64_t &j0, int64_t &j1) -> bool {
-        v = t.level_node[e];
-        if (v < sp.n0 || v >= sp.n1 || t.level[v] != l) return false;
-        j0 = t.in_ptr[v], j1 = t.in_ptr[v + 1];
-        return j0 >= sp.a0 && j0 <= j1 && j1 <= sp.a1;
-    };
-    auto in_arc_at = [&](int64_t j, int64_t v, int64_t l, int64_t &a, int64_t &u, int64_t &g) -> bool {
-        a = t.in_arc[j];
-        if (a < sp.a0 || a >= sp.a1) return false;
-        u = sp.n0 + t.src[a], g = t.arc[a];
-        if (sp.n0 + t.dst[a] != v || u < sp.n0 || u >= sp.n1 || g < 0 || g >= t.G) return false;
-        const int32_t lu = t.level[u];
-        return lu >= sp.l0 && lu < l;            // the level must rise: u is final
-    };
 
     for (int64_t v = sp.n0 + tid; v < sp.n1; v += NT)
         if (t.time[v] == 0 && t.state[v] == t.start) atomicMin(&s_start, (unsigned long long)v);
@@ -163,12 +87,12 @@ __global__ __launch_bounds__(NT) void lattice_oracle_kernel(const OracleArgs q) 
     // forward, levels upwards: a wave owns a node and takes its in-arcs in turn
     for (int64_t l = sp.l0; l < sp.l1 && st >= 0; ++l) {
         const int64_t e0 = t.level_ptr[l], e1 = t.level_ptr[l + 1];
-        if (e0 < sp.n0 || e0 > e1 || e1 > sp.n1) {
+        if (!level_range(e0, e1, sp.n0, sp.n1)) {
             bad = true;
         } else {
             for (int64_t e = e0 + wave; e < e1; e += NW) {      // everything but the position is uniform in the wave
                 int64_t v, j0, j1;
-                if (!node_at(e, l, v, j0, j1)) {
+                if (!node_at(t, sp, e, l, v) || !in_arcs_of(t, sp, v, j0, j1)) {
                     bad = true;
                     continue;
                 }
@@ -185,7 +109,7 @@ __global__ __launch_bounds__(NT) void lattice_oracle_kernel(const OracleArgs q) 
                     int32_t m = UNREACHABLE;
                     for (int64_t j = j0; j < j1; ++j) {
                         int64_t a, u, g;
-                        if (!in_arc_at(j, v, l, a, u, g)) {
+                        if (!in_arc_at(t, sp, j, v, l, a, u, g)) {
                             bad = true;
                             break;
                         }
@@ -212,7 +136,7 @@ __global__ __launch_bounds__(NT) void lattice_oracle_kernel(const OracleArgs q) 
     // the end node: the least D(v, R), the smallest node among the minima
     if (!dead && st >= 0) {
         for (int64_t v = sp.n0 + tid; v < sp.n1; v += NT) {
-            if (!(scaled_end(t, v, frames, reached, 1.0, bad) < DINF)) continue;
+            if (!(end_cost(t, v, frames, reached, bad) < DINF)) continue;
             const int32_t d = D[v * C + R];
             if (d >= 0 && d < UNREACHABLE)
                 atomicMin(&s_best, ((unsigned long long)(uint32_t)d << 32) | (unsigned long long)(v - sp.n0));
@@ -239,8 +163,8 @@ __global__ __launch_bounds__(NT) void lattice_oracle_kernel(const OracleArgs q) 
                 break;
             }
             const int64_t lv = t.level[v];
-            const int64_t j0 = t.in_ptr[v], j1 = t.in_ptr[v + 1];
-            if (lv < sp.l0 || lv >= sp.l1 || j0 < sp.a0 || j0 > j1 || j1 > sp.a1) {
+            int64_t j0, j1;
+            if (lv < sp.l0 || lv >= sp.l1 || !in_arcs_of(t, sp, v, j0, j1)) {
                 bad = true;
                 break;
             }
@@ -253,7 +177,7 @@ __global__ __launch_bounds__(NT) void lattice_oracle_kernel(const OracleArgs q) 
                 bool hit = false, wrong = false;
                 if (j < j1) {
                     int64_t a, u, g;
-                    if (!in_arc_at(j, v, lv, a, u, g)) {
+                    if (!in_arc_at(t, sp, j, v, lv, a, u, g)) {
                         wrong = true;
                     } else {
                         my_a = (int32_t)(a - sp.a0), my_u = (int32_t)(u - sp.n0), my_w = t.ol[g];
@@ -330,21 +254,6 @@ __global__ __launch_bounds__(NT) void lattice_oracle_kernel(const OracleArgs q) 
     }
 }
 
-bool sizes_ok(int64_t N, int64_t A, int64_t L) {
-    const int64_t lim = ((int64_t)1 << 31) - 1;
-    return N >= 0 && A >= 0 && L >= 0 && N < lim && A < lim && L < lim;
-}
-
-// the host copies of the offsets: [B + 1], from 0 to total, never decreasing
-bool offsets_ok(const int64_t *h, int B, int64_t total) {
-    if (!h || h[0] != 0 || h[B] != total) return false;
-    for (int b = 0; b < B; ++b)
-        if (h[b + 1] < h[b]) return false;
-    return true;
-}
-
-bool threads_ok(int threads) { return threads == 0 || threads == 64 || threads == 128 || threads == 256; }
-
 }  // namespace
 
 extern "C" int asr_lattice_oracle_supported(int64_t N, int64_t A, int64_t L, int max_words) {
@@ -368,22 +277,12 @@ extern "C" int asr_lattice_oracle_i32(
     const int32_t *ref_num_words, int max_words, int32_t *out_errors, int32_t *out_counts, int32_t *out_num_words,
     int32_t *out_words, int32_t *out_ref_frames, double *out_cost, int32_t *out_status, void *workspace,
     int64_t workspace_bytes, void *stream) {
-    const int64_t S = num_states, G = num_graph_arcs;
-    if (B < 0 || b_begin < 0 || b_count < 0 || (int64_t)b_begin + b_count > B) return ASR_EINVAL;
-    if (N < 0 || A < 0 || L < 0 || S < 1 || G < 0 || start < 0 || start >= S) return ASR_EINVAL;
-    if (!sizes_ok(N, A, L)) return ASR_EUNSUPPORTED;
-    if (!offsets_ok(h_node_off, B, N) || !offsets_ok(h_arc_off, B, A) || !offsets_ok(h_level_off, B, L))
-        return ASR_EINVAL;
-    for (int b = 0; b < B; ++b) {               // a level holds a node; arcs need two nodes on two levels
-        const int64_t n = h_node_off[b + 1] - h_node_off[b], l = h_level_off[b + 1] - h_level_off[b];
-        if (l > n || (n > 0 && l < 1) || (h_arc_off[b + 1] > h_arc_off[b] && l < 2)) return ASR_EINVAL;
-    }
-    if (!node_off || !arc_off || !level_off || !level_ptr || !in_ptr || !out_ptr || !num_frames || !reached_final ||
-        !own_scale || !final_cost)
-        return ASR_EINVAL;
-    if (N > 0 && (!node_time || !node_state || !node_level || !level_node)) return ASR_EINVAL;
-    if (A > 0 && (!lat_src || !lat_dst || !lat_arc || !lat_lp || !in_arc || !arc_weight || !arc_olabel))
-        return ASR_EINVAL;
+    OracleArgs q;
+    const int rc = fill_lat(q.t, LAT_LP | LAT_OLABEL, B, b_begin, b_count, N, A, L, h_node_off, h_arc_off, h_level_off,
+                            node_off, arc_off, level_off, node_time, node_state, node_level, lat_src, lat_dst, lat_arc,
+                            lat_lp, level_ptr, level_node, in_ptr, in_arc, out_ptr, num_frames, reached_final,
+                            own_scale, num_states, num_graph_arcs, arc_weight, arc_olabel, nullptr, final_cost, start);
+    if (rc != ASR_OK) return rc;
     if (max_words < 1 || !threads_ok(threads)) return ASR_EINVAL;
     if (max_words > ORACLE_MAX_WORDS || L + max_words >= UNREACHABLE) return ASR_EUNSUPPORTED;
     if (b_count == 0) return ASR_OK;
@@ -393,11 +292,6 @@ extern "C" int asr_lattice_oracle_i32(
     const int64_t n = h_node_off[b_begin + b_count] - h_node_off[b_begin];
     const int64_t need = asr_lattice_oracle_workspace_bytes(n, max_words);
     if (need <= 0 || !workspace || workspace_bytes < need) return ASR_EINVAL;
-    OracleArgs q;
-    q.t = Lat{B, N, A, L, G, S, node_off, arc_off, level_off, node_time, node_state, node_level, lat_src, lat_dst,
-              lat_arc, lat_lp, level_ptr, level_node, in_ptr, in_arc, num_frames, reached_final, own_scale,
-              arc_weight, final_cost, arc_olabel, start, b_begin, b_count, h_node_off[b_begin],
-              h_node_off[b_begin + b_count]};
     q.ac_scale = acoustic_scale;
     q.lm_scale = lm_scale;
     q.ref_words = ref_words;
@@ -412,11 +306,7 @@ extern "C" int asr_lattice_oracle_i32(
     q.out_frames = out_ref_frames;
     q.out_cost = out_cost;
     q.out_status = out_status;
-    const dim3 grid((unsigned)b_count);
-    switch (threads) {                          // 0: four waves, four nodes of a level at a time
-    case 64: hipLaunchKernelGGL(lattice_oracle_kernel<64>, grid, dim3(64), 0, (hipStream_t)stream, q); break;
-    case 128: hipLaunchKernelGGL(lattice_oracle_kernel<128>, grid, dim3(128), 0, (hipStream_t)stream, q); break;
-    default: hipLaunchKernelGGL(lattice_oracle_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, q); break;
-    }
-    return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
+    // threads 0: four waves, four nodes of a level at a time
+    return launch_by_threads(threads, 256, b_count, stream, q, lattice_oracle_kernel<64>, lattice_oracle_kernel<128>,
+                             lattice_oracle_kernel<256>);
 }

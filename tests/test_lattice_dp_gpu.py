@@ -363,6 +363,29 @@ def test_env_switch(monkeypatch):
     assert_log_close(batch.posteriors(0.5).arc_log_post, post.arc_log_post.cpu().numpy(), 'env')
 
 
+def test_a_malformed_batch_is_refused():
+    """tensors changed behind the constructor's checks: the kernels' own range checks answer.  best_paths never
+    reads out_ptr (it walks the in-arcs only), so that field is posteriors' alone; posteriors does not count
+    its launches, its message is the one raised on the status words the kernel wrote."""
+    import nbest_cases as NC
+    lats, _ = NC.toy_lattices('a', 1.0, 2.0)
+    turned = int(np.nonzero(lats[0].src != lats[0].dst)[0][0])
+    fields = (('dst', 3, 10 ** 6), ('arc', 1, 10 ** 6), ('node_level', 0, 10 ** 6), ('out_ptr', 2, 10 ** 6),
+              ('level_node', 1, 10 ** 6), ('in_ptr', 2, 10 ** 6), ('in_arc', 1, 10 ** 6), ('src', 3, 10 ** 6),
+              ('dst', turned, None))                    # None: the arc turned round, its level does not rise
+    for field, index, value in fields:
+        for op, entry in (('best_paths', 'asr_lattice_bestpath_f64'), ('posteriors', 'asr_lattice_posterior_f64')):
+            if (op, field) == ('best_paths', 'out_ptr'):
+                continue
+            with quiet():
+                batch = DeviceLatticeBatch.from_lattices(lats, dev())
+            getattr(batch, field)[index] = batch.src[index] if value is None else value
+            with pytest.raises(ValueError, match=entry + '.*inconsistent'):
+                getattr(batch, op)()
+            if op == 'best_paths':
+                assert batch.launches == 1
+
+
 def test_the_entry_points_are_exported():
     L = lib()
     assert L.asr_lattice_bestpath_supported(1000, 5000, 300) == 1
