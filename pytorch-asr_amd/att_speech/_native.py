@@ -29,6 +29,12 @@ _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_floa
 
 # the LM of asr_lattice_lmrescore_*: states, arcs, six CSR / back-off arrays, start, label map and length, oov cost
 _LM_ARGS = [_i64, _i64] + [_vp] * 6 + [_i, _vp, _i64, ctypes.c_double]
+# DeviceLatticeBatch._common_args, shared by the six lattice DP launches: nodes, arcs, levels and the batch's 21
+# arrays; after the two scales the graph's states, arcs, three arrays and start, and the threads a workgroup
+_LAT_HEAD = [_i64, _i64, _i64] + [_vp] * 21
+_LAT_TAIL = [_i64, _i64] + [_vp] * 3 + [_i, _i]
+_LAT_SCALES = [ctypes.c_double] * 2
+_WS = [_vp, _i64, _vp]          # workspace, its bytes, stream
 
 _SIGNATURES = {
     'asr_abi_version': (ctypes.c_int, []),
@@ -94,31 +100,24 @@ _SIGNATURES = {
                                   _f, _f, _f, _i, _i64, _i64, _i64, _i64, _i] + [_vp] * 14 + [_i64, _vp]),
     'asr_lattice_bestpath_supported': (_i, [_i64, _i64, _i64]),
     'asr_lattice_bestpath_workspace_bytes': (_i64, [_i64, _i]),
-    'asr_lattice_bestpath_f64': (_i, [_i, _i, _i, _i, _i64, _i64, _i64] + [_vp] * 23 + [_i64, _i64] + [_vp] * 3 +
-                                 [_i, _i] + [_vp] * 5 + [_i64, _vp]),
+    'asr_lattice_bestpath_f64': (_i, [_i] * 4 + _LAT_HEAD + [_vp] * 2 + _LAT_TAIL + [_vp] * 4 + _WS),
     'asr_lattice_posterior_supported': (_i, [_i64, _i64, _i64]),
     'asr_lattice_posterior_workspace_bytes': (_i64, [_i64]),
-    'asr_lattice_posterior_f64': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
-                                  [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 5 + [_i64, _vp]),
+    'asr_lattice_posterior_f64': (_i, [_i] * 3 + _LAT_HEAD + _LAT_SCALES + _LAT_TAIL + [_vp] * 4 + _WS),
     'asr_lattice_nbest_supported': (_i, [_i64, _i64, _i64, _i]),
     'asr_lattice_nbest_workspace_bytes': (_i64, [_i64, _i]),
-    'asr_lattice_nbest_f64': (_i, [_i, _i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
-                              [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 6 + [_i64, _vp]),
+    'asr_lattice_nbest_f64': (_i, [_i] * 4 + _LAT_HEAD + _LAT_SCALES + _LAT_TAIL + [_vp] * 5 + _WS),
     'asr_lattice_mbr_supported': (_i, [_i64, _i64, _i64, _i]),
     'asr_lattice_mbr_workspace_bytes': (_i64, [_i64, _i]),
-    'asr_lattice_mbr_f64': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
-                            [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 4 + [_i, _i, _i64] + [_vp] * 11 +
-                            [_vp, _i64, _vp]),
+    'asr_lattice_mbr_f64': (_i, [_i] * 3 + _LAT_HEAD + _LAT_SCALES + _LAT_TAIL + [_vp] * 4 + [_i, _i, _i64] +
+                            [_vp] * 11 + _WS),
     'asr_lattice_oracle_supported': (_i, [_i64, _i64, _i64, _i]),
     'asr_lattice_oracle_workspace_bytes': (_i64, [_i64, _i]),
-    'asr_lattice_oracle_i32': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
-                               [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 2 + [_i] + [_vp] * 7 +
-                               [_vp, _i64, _vp]),
+    'asr_lattice_oracle_i32': (_i, [_i] * 3 + _LAT_HEAD + _LAT_SCALES + _LAT_TAIL + [_vp] * 2 + [_i] + [_vp] * 7 + _WS),
     'asr_lattice_seqtrain_supported': (_i, [_i64, _i64, _i64]),
     'asr_lattice_seqtrain_workspace_bytes': (_i64, [_i64]),
-    'asr_lattice_seqtrain_f64': (_i, [_i, _i, _i, _i64, _i64, _i64] + [_vp] * 21 + [ctypes.c_double] * 2 +
-                                 [_i64, _i64] + [_vp] * 3 + [_i, _i] + [_vp] * 2 + [_i, _i, _vp, _i,
-                                 ctypes.c_double, _i64, _i64] + [_vp] * 8 + [_vp, _i64, _vp]),
+    'asr_lattice_seqtrain_f64': (_i, [_i] * 3 + _LAT_HEAD + _LAT_SCALES + _LAT_TAIL + [_vp] * 2 + [_i, _i, _vp, _i,
+                                 ctypes.c_double, _i64, _i64] + [_vp] * 8 + _WS),
     'asr_lattice_lmrescore_supported': (_i, [_i64, _i64, _i64, _i]),
     'asr_lattice_lmrescore_workspace_bytes': (_i64, [_i64, _i]),
     'asr_lattice_lmrescore_expand': (_i, [_i] * 4 + [_i64] * 3 + [_vp] * 11 + [_i64, _vp, _i] + _LM_ARGS + [_vp] * 3 +

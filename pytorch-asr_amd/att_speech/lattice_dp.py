@@ -15,10 +15,12 @@ and `depth` is lattice-depth.  `seq_objective` is the training side: the lattice
 the sMBR objective from the live log_probs, with the occupancies as a [T, B, C] tensor, in one launch of
 asr_lattice_seqtrain_f64 (csrc/lattice_train.hip, section 4.26; att_speech.lattice_train wraps it in autograd).
 
-A batch on a GPU runs asr_lattice_bestpath_f64 / asr_lattice_posterior_f64 / asr_lattice_nbest_f64
-(csrc/lattice_dp.hip); a batch of CPU tensors, or ASR_LATTICE_DP_NATIVE=0 (ASR_LATTICE_NBEST_NATIVE=0
-for nbest; both read per call), the host path: LatticeBatch of att_speech.wfst_lattice, which gives
-the same bits for best paths and n-best lists and the same posteriors within rounding.
+A batch on a GPU runs the six entry points asr_lattice_bestpath_f64, asr_lattice_posterior_f64, asr_lattice_nbest_f64,
+asr_lattice_mbr_f64, asr_lattice_oracle_i32 and asr_lattice_seqtrain_f64, all through one chunked launch
+(DeviceLatticeBatch._launch); a batch of CPU tensors, or ASR_LATTICE_<NAME>_NATIVE=0 (DP for
+best_paths and posteriors, NBEST, MBR, ORACLE, TRAIN; read per call), the host path: LatticeBatch of
+att_speech.wfst_lattice, which gives the same bits for best paths, n-best lists and the oracle, and the same
+posteriors, MBR results and training statistics within rounding.
 """
 import ctypes
 import os
@@ -103,6 +105,7 @@ class DeviceLatticeBatch(object):
         self.max_frames = int(self.num_frames.max()) if max_frames is None and B else int(max_frames or 0)
         self.num_classes = graph.max_ilabel if num_classes is None else int(num_classes)
         self.workspace_bytes = int(workspace_bytes)
+        self.launches = 0                       # the kernel launches of the last operation that ran on the device
         self._host = None
         self._emission = {}                     # (T, C) -> the emission index of seq_objective
         self._build_levels()
@@ -168,7 +171,10 @@ class DeviceLatticeBatch(object):
 
     @property
     def ilabel(self):
-        """[A] the input label of every arc (0: epsilon), on the device"""
+        """[A] the input label of every arc (0: epsilon), on the device.  The gather itself checks nothing, so an
+        arc index changed behind the constructor's checks raises ValueError here: one reduction, one read-back"""
+        if self.num_arcs and bool(((self.arc < 0) | (self.arc >= len(self.graph.src))).any()):
+            raise ValueError("ilabel: an arc index outside the graph: the batch's index arrays are inconsistent")
         return self.graph.device_arrays(self.device)['il'][self.arc]
 
     # ---- construction ---------------------------------------------------------------------
@@ -207,8 +213,9 @@ class DeviceLatticeBatch(object):
             self._host = LatticeBatch(self.lattices())
         return self._host
 
-    def _on_device(self):
-        return self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_DP_NATIVE', '1') != '0'
+    def _native_path(self, name):
+        """a batch on a GPU, unless ASR_LATTICE_<name>_NATIVE=0 (read per call)"""
+        return self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_%s_NATIVE' % name, '1') != '0'
 
     def _common_args(self):
         p = _native._p
@@ -243,6 +250,49 @@ class DeviceLatticeBatch(object):
             raise ValueError("%s: %s" % (what, _native.lib().asr_strerror(code).decode()))
         _native.check(code, what)
 
+    def _budget(self, workspace_bytes):
+        return int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
+
+    def _launch(self, entry, size, bytes_per_node, slack, workspace_bytes, lead, scales, args, supported=None):
+        """The chunked launch of all six operations.  Asks asr_lattice_<op>_supported (nodes, arcs, levels and
+        `size`, or `supported` in its place), plans the utterance chunks that fit workspace_bytes (default: the
+        batch's) less `slack` at bytes_per_node, allocates one workspace for the biggest chunk
+        (asr_lattice_<op>_workspace_bytes(nodes, *size)) and calls, once per chunk,
+        entry(B, b0, b1 - b0, *lead, *head, *scales, *tail, *args, ws, nbytes, stream).  Returns the number of
+        launches, for self.launches.  scales: (acoustic, LM) numbers, None for NaN (the lattice's own scale), or
+        best_paths' two pointers.  What the launches wrote, the status words among it, is the caller's to read back."""
+        L = _native.lib()
+        stem = entry.rsplit('_', 1)[0]
+        if not getattr(L, stem + '_supported')(self.num_nodes, self.num_arcs, self.num_levels,
+                                                *(size if supported is None else supported)):
+            raise NotImplementedError("%s: the batch is too large" % entry)
+        chunks = self._utterance_chunks(bytes_per_node, self._budget(workspace_bytes) - slack)
+        nbytes = getattr(L, stem + '_workspace_bytes')(
+            max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks), *size)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        head, tail = self._common_args()
+        scales = [x if isinstance(x, ctypes.c_void_p) else float('nan' if x is None else x) for x in scales]
+        run, B = getattr(L, entry), self.num_utterances
+        for b0, b1 in chunks:
+            self._check(run(B, b0, b1 - b0, *lead, *head, *scales, *tail, *args, _native._p(ws), nbytes,
+                            _native._stream()), entry)
+        return len(chunks)
+
+    @staticmethod
+    def _refuse_bad_status(status, entry, mask=-1):
+        """status: the launches' status words on the host; mask: the bits that say the index arrays were refused"""
+        if (status & mask).any():
+            raise ValueError("%s: the batch's index arrays are inconsistent" % entry)
+
+    def _redo_on_host(self, out, redo, warning, run):
+        """out with the utterances `redo` replaced by run(LatticeBatch of them), the host twin's results"""
+        if redo:
+            warnings.warn(warning)
+            lats = self._host_batch().lattices
+            for b, r in zip(redo, run(LatticeBatch([lats[b] for b in redo]))):
+                out[b] = r
+        return out
+
     # ---- the tropical sweep -----------------------------------------------------------------
     def best_paths(self, acoustic_scales=None, lm_scales=1.0, workspace_bytes=None):
         """The best path of every lattice under every (acoustic scale, LM scale) pair.
@@ -260,20 +310,15 @@ class DeviceLatticeBatch(object):
         if len(lms) != len(acs):
             raise ValueError("lm_scales must be a float or as long as acoustic_scales")
         P, B = len(acs), self.num_utterances
-        if not self._on_device():
+        if not self._native_path('DP'):
             hb = self._host_batch()
             with np.errstate(invalid='ignore'):
                 return [hb.best_paths(sc, lm) for sc, lm in zip(acs, lms)]
         none = ([], INF, INF, INF)
         if P == 0 or B == 0 or self.num_nodes == 0:
             return [[none] * B for _ in range(P)]
-        L = _native.lib()
-        if not L.asr_lattice_bestpath_supported(self.num_nodes, self.num_arcs, self.num_levels):
-            raise NotImplementedError("asr_lattice_bestpath_f64: the batch is too large")
-        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
         dev, p = self.device, _native._p
-        per_launch = max(1, min(P, (budget - 64) // max(1, 12 * self.num_nodes)))
-        chunks = self._utterance_chunks(12 * per_launch, budget)
+        per_launch = max(1, min(P, (self._budget(workspace_bytes) - 64) // max(1, 12 * self.num_nodes)))
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         ac_d = torch.tensor([float('nan') if a is None else float(a) for a in acs], **f64)
@@ -282,22 +327,13 @@ class DeviceLatticeBatch(object):
         n_words = torch.zeros((P, B), **i32)
         words = torch.zeros((P, max(1, self.num_levels)), **i32)
         status = torch.zeros((P, B), **i32)
-        head, tail = self._common_args()
-        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
-        nbytes = L.asr_lattice_bestpath_workspace_bytes(biggest, per_launch)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.launches = 0
-        for p0 in range(0, P, per_launch):
-            np_ = min(per_launch, P - p0)
-            for b0, b1 in chunks:
-                self._check(L.asr_lattice_bestpath_f64(
-                    B, b0, b1 - b0, np_, *head, p(ac_d[p0:]), p(lm_d[p0:]), *tail,
-                    p(cost[p0:]), p(n_words[p0:]), p(words[p0:]), p(status[p0:]), p(ws), nbytes,
-                    _native._stream()), 'asr_lattice_bestpath_f64')
-                self.launches += 1
+        self.launches = sum(                    # a group of pairs: the same chunks and workspace size every time
+            self._launch('asr_lattice_bestpath_f64', (per_launch,), 12 * per_launch, 0, workspace_bytes,
+                         (min(per_launch, P - p0),), (p(ac_d[p0:]), p(lm_d[p0:])),
+                         (p(cost[p0:]), p(n_words[p0:]), p(words[p0:]), p(status[p0:])), supported=())
+            for p0 in range(0, P, per_launch))
         cost_h, nw_h, words_h = cost.cpu().numpy(), n_words.cpu().numpy(), words.cpu().numpy()
-        if status.cpu().numpy().any():
-            raise ValueError("asr_lattice_bestpath_f64: the batch's index arrays are inconsistent")
+        self._refuse_bad_status(status.cpu().numpy(), 'asr_lattice_bestpath_f64')
         out = []
         for k in range(P):
             row = []
@@ -324,17 +360,14 @@ class DeviceLatticeBatch(object):
         NBEST_DEVICE_MAX run LatticeBatch.nbest on a copy: the same bits in every case."""
         n = int(n)
         B = self.num_utterances
-        native = (self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_NBEST_NATIVE', '1') != '0'
-                  and n <= NBEST_DEVICE_MAX)
-        if not native:
+        if not (self._native_path('NBEST') and n <= NBEST_DEVICE_MAX):
             return self._host_batch().nbest(n, acoustic_scale, lm_scale)
         if n < 1 or B == 0 or self.num_nodes == 0:
             return [[] for _ in range(B)]
         count, status, cost, n_words, words = self._nbest_launch(n, acoustic_scale, lm_scale, workspace_bytes)
         packed = torch.cat([count, status, n_words.reshape(-1)]).cpu().numpy()     # the small ones in one read-back
         count_h, status_h, nw_h = packed[:B], packed[B:2 * B], packed[2 * B:].reshape(B, n)
-        if status_h.any():
-            raise ValueError("asr_lattice_nbest_f64: the batch's index arrays are inconsistent")
+        self._refuse_bad_status(status_h, 'asr_lattice_nbest_f64')
         cost_h, words_h = cost.cpu().numpy(), words.cpu().numpy()
         levels = np.diff(self.level_off)
         utt, rows, costs = [], [], []
@@ -350,29 +383,15 @@ class DeviceLatticeBatch(object):
     def _nbest_launch(self, n, acoustic_scale, lm_scale, workspace_bytes):
         """the launches of nbest alone: (count [B], status [B], cost [B, n], n_words [B, n], words [n L]) on
         the device, as asr_lattice_nbest_f64 leaves them"""
-        B = self.num_utterances
-        L = _native.lib()
-        if not L.asr_lattice_nbest_supported(self.num_nodes, self.num_arcs, self.num_levels, n):
-            raise NotImplementedError("asr_lattice_nbest_f64: the batch is too large")
-        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
-        dev, p = self.device, _native._p
-        chunks = self._utterance_chunks(28 * n + 4, budget - 128)       # 128: the rounding of the six arrays
-        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
-        nbytes = L.asr_lattice_nbest_workspace_bytes(biggest, n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        B, dev, p = self.num_utterances, self.device, _native._p
         i32 = dict(dtype=torch.int32, device=dev)
         count, status = torch.zeros(B, **i32), torch.zeros(B, **i32)
         cost = torch.empty((B, n), dtype=torch.float64, device=dev)
         n_words = torch.zeros((B, n), **i32)
         words = torch.zeros(n * max(1, self.num_levels), **i32)
-        head, tail = self._common_args()
-        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
-        self.launches = 0
-        for b0, b1 in chunks:
-            self._check(L.asr_lattice_nbest_f64(
-                B, b0, b1 - b0, n, *head, sc, float(lm_scale), *tail, p(count), p(cost), p(n_words), p(words),
-                p(status), p(ws), nbytes, _native._stream()), 'asr_lattice_nbest_f64')
-            self.launches += 1
+        self.launches = self._launch(           # 128: the rounding of the six arrays
+            'asr_lattice_nbest_f64', (n,), 28 * n + 4, 128, workspace_bytes, (n,), (acoustic_scale, lm_scale),
+            (p(count), p(cost), p(n_words), p(words), p(status)))
         return count, status, cost, n_words, words
 
     def sentences(self, n, **kw):
@@ -408,28 +427,19 @@ class DeviceLatticeBatch(object):
         def host(x):
             return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
         self.launches = 0
-        native = self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_MBR_NATIVE', '1') != '0'
-        if not native:
+        if not self._native_path('MBR'):
             return self._host_batch().mbr(acoustic_scale, lm_scale, max_iterations, hypotheses, host(arc_cond),
                                           host(end_cond))
         if B == 0 or self.num_nodes == 0:
             return [MBR_NONE] * B
-        L = _native.lib()
         levels = np.diff(self.level_off)
         W = int(levels.max()) if max_words is None else int(max_words)
         W = max(1, min(W, MBR_DEVICE_MAX_WORDS))
-        if not L.asr_lattice_mbr_supported(self.num_nodes, self.num_arcs, self.num_levels, W):
-            raise NotImplementedError("asr_lattice_mbr_f64: the batch is too large")
         if getattr(self, '_mbr_labels', None) is None:     # the graph's distinct words, and 0: no slot holds more
             ol = np.asarray(self.graph.olabel)
             self._mbr_labels = int(len(np.unique(ol[ol != 0]))) + 1
         cap = int(MBR_SAUSAGE_ENTRIES) or min(self._mbr_labels, 64) * (2 * W + 2)
-        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
         dev, p = self.device, _native._p
-        chunks = self._utterance_chunks(16 * (2 * W + 2) + 8, budget - 64)
-        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
-        nbytes = L.asr_lattice_mbr_workspace_bytes(biggest, W)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
 
@@ -454,18 +464,13 @@ class DeviceLatticeBatch(object):
         words, frames = torch.zeros((B, W), **i32), torch.zeros((B, W), **i32)
         conf, risk = torch.zeros((B, W), **f64), torch.full((B,), INF, **f64)
         table = torch.full((3, B, cap), -1, dtype=torch.int64, device=dev)
-        head, tail = self._common_args()
-        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
-        for b0, b1 in chunks:
-            self._check(L.asr_lattice_mbr_f64(
-                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(arc_cond), p(end_cond), p(init_w), p(init_n),
-                int(max_iterations), W, cap, p(small[0]), p(words), p(conf), p(frames), p(risk), p(small[1]),
-                p(small[2]), p(small[3]), p(table[0]), p(table[1]), p(table[2]), p(ws), nbytes,
-                _native._stream()), 'asr_lattice_mbr_f64')
-            self.launches += 1
+        self.launches = self._launch(
+            'asr_lattice_mbr_f64', (W,), 16 * (2 * W + 2) + 8, 64, workspace_bytes, (), (acoustic_scale, lm_scale),
+            (p(arc_cond), p(end_cond), p(init_w), p(init_n), int(max_iterations), W, cap, p(small[0]), p(words),
+             p(conf), p(frames), p(risk), p(small[1]), p(small[2]), p(small[3]), p(table[0]), p(table[1]),
+             p(table[2])))
         nw_h, it_h, status_h, _ = small.cpu().numpy()
-        if (status_h & 1).any():
-            raise ValueError("asr_lattice_mbr_f64: the batch's index arrays are inconsistent")
+        self._refuse_bad_status(status_h, 'asr_lattice_mbr_f64', 1)
         used = torch.nonzero(((table[0] >= 0) & (table[1] > 0)).reshape(-1)).reshape(-1)    # the entries alone cross
         t_utt = torch.div(used, cap, rounding_mode='floor').cpu().numpy()
         t_key, t_gamma, t_tau = (table[j].reshape(-1)[used].cpu().numpy() for j in range(3))
@@ -483,20 +488,16 @@ class DeviceLatticeBatch(object):
             out.append(MBRResult(words_h[b, :n].tolist(), conf_h[b, :n].tolist(), frames_h[b, :n].tolist(),
                                  float(risk_h[b]), int(it_h[b]), mbr_sausage(tables[b])))
         redo = np.nonzero(status_h)[0].tolist()
-        if redo:
-            warnings.warn("mbr: %d of %d utterances outgrew the device's %d words a hypothesis or %d sausage "
-                          "entries and were redone on the host" % (len(redo), B, W, cap))
-            lats = self._host_batch().lattices
+
+        def twin(sub):
             ac, ec = host(arc_cond), host(end_cond)
             pick = np.concatenate
-            sub = LatticeBatch([lats[b] for b in redo]).mbr(
-                acoustic_scale, lm_scale, max_iterations,
-                None if hypotheses is None else [hypotheses[b] for b in redo],
-                None if ac is None else pick([ac[self.arc_off[b]:self.arc_off[b + 1]] for b in redo]),
-                None if ec is None else pick([ec[self.node_off[b]:self.node_off[b + 1]] for b in redo]))
-            for b, r in zip(redo, sub):
-                out[b] = r
-        return out
+            return sub.mbr(acoustic_scale, lm_scale, max_iterations,
+                           None if hypotheses is None else [hypotheses[b] for b in redo],
+                           None if ac is None else pick([ac[self.arc_off[b]:self.arc_off[b + 1]] for b in redo]),
+                           None if ec is None else pick([ec[self.node_off[b]:self.node_off[b + 1]] for b in redo]))
+        return self._redo_on_host(out, redo, "mbr: %d of %d utterances outgrew the device's %d words a hypothesis or "
+                                  "%d sausage entries and were redone on the host" % (len(redo), B, W, cap), twin)
 
     def expected_errors(self, sentences, acoustic_scale=None, lm_scale=1.0, **kw):
         """The expected word edit distance of given sentences over their lattices: `sentences` holds a
@@ -533,23 +534,14 @@ class DeviceLatticeBatch(object):
         B = self.num_utterances
         refs = _oracle_references(references, B)
         self.launches = 0
-        native = self.device.type == 'cuda' and os.environ.get('ASR_LATTICE_ORACLE_NATIVE', '1') != '0'
-        if not native:
+        if not self._native_path('ORACLE'):
             return self._host_batch().oracle(refs, acoustic_scale, lm_scale)
         if B == 0 or self.num_nodes == 0:
             return [ORACLE_NONE] * B
         limit = max(1, min(int(ORACLE_DEVICE_MAX_WORDS), 1023))
         redo = [b for b, r in enumerate(refs) if len(r) > limit]
         W = max([1] + [len(r) for r in refs if len(r) <= limit])
-        L = _native.lib()
-        if not L.asr_lattice_oracle_supported(self.num_nodes, self.num_arcs, self.num_levels, W):
-            raise NotImplementedError("asr_lattice_oracle_i32: the batch is too large")
-        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
         dev, p = self.device, _native._p
-        chunks = self._utterance_chunks(4 * (W + 1), budget - 64)
-        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
-        nbytes = L.asr_lattice_oracle_workspace_bytes(biggest, W)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         rows = np.zeros((B, W), np.int32)
         counts = np.zeros(B, np.int32)
         for b, r in enumerate(refs):
@@ -563,18 +555,12 @@ class DeviceLatticeBatch(object):
         words = torch.zeros(max(1, self.num_levels), **i32)
         frames = torch.zeros((B, W), **i32)
         cost = torch.full((B,), INF, dtype=torch.float64, device=dev)
-        head, tail = self._common_args()
-        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
-        for b0, b1 in chunks:
-            self._check(L.asr_lattice_oracle_i32(
-                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(ref_w), p(ref_n), W, p(small[0]), p(counts_d),
-                p(small[2]), p(words), p(frames), p(cost), p(small[1]), p(ws), nbytes, _native._stream()),
-                'asr_lattice_oracle_i32')
-            self.launches += 1
+        self.launches = self._launch(
+            'asr_lattice_oracle_i32', (W,), 4 * (W + 1), 64, workspace_bytes, (), (acoustic_scale, lm_scale),
+            (p(ref_w), p(ref_n), W, p(small[0]), p(counts_d), p(small[2]), p(words), p(frames), p(cost), p(small[1])))
         small_h = small.cpu().numpy()
         err_h, status_h, nw_h, ops_h = small_h[0], small_h[1], small_h[2], small_h[3:].reshape(B, 4)
-        if (status_h & 1).any():
-            raise ValueError("asr_lattice_oracle_i32: the batch's index arrays are inconsistent")
+        self._refuse_bad_status(status_h, 'asr_lattice_oracle_i32', 1)
         words_h, frames_h, cost_h = words.cpu().numpy(), frames.cpu().numpy(), cost.cpu().numpy()
         out = []
         for b in range(B):
@@ -585,14 +571,9 @@ class DeviceLatticeBatch(object):
             n_sub, n_ins, n_del, n_cor = (int(x) for x in ops_h[b])
             out.append(OracleResult(int(err_h[b]), n_sub, n_ins, n_del, n_cor, words_h[o:o + nw_h[b]].tolist(),
                                     frames_h[b, :len(refs[b])].tolist(), float(cost_h[b])))
-        if redo:
-            warnings.warn("oracle: %d of %d utterances have a reference of more than the device's %d words and "
-                          "were redone on the host" % (len(redo), B, limit))
-            lats = self._host_batch().lattices
-            sub = LatticeBatch([lats[b] for b in redo]).oracle([refs[b] for b in redo], acoustic_scale, lm_scale)
-            for b, r in zip(redo, sub):
-                out[b] = r
-        return out
+        return self._redo_on_host(out, redo, "oracle: %d of %d utterances have a reference of more than the device's "
+                                  "%d words and were redone on the host" % (len(redo), B, limit),
+                                  lambda sub: sub.oracle([refs[b] for b in redo], acoustic_scale, lm_scale))
 
     def depth(self):
         """per utterance the emitting lattice arcs per frame (Kaldi's lattice-depth), 0.0 for an empty lattice:
@@ -640,8 +621,8 @@ class DeviceLatticeBatch(object):
         as in best_paths: a LatticePosteriors (log_z [B], arc_log_post [A], node_log_post [N] in
         fp64, frame_posteriors(), word_posteriors()).  On a GPU one launch of
         asr_lattice_posterior_f64 does forward and backward (several when workspace_bytes does not
-        hold 16 bytes per node at once); two runs give the same bits."""
-        if not self._on_device():
+        hold 16 bytes per node at once; self.launches counts them); two runs give the same bits."""
+        if not self._native_path('DP'):
             post = self._host_batch().posteriors(acoustic_scale, lm_scale)
             if self.device.type == 'cuda':
                 post = LatticePosteriors(self, *[torch.from_numpy(np.asarray(x, np.float64)).to(self.device) for x in
@@ -656,23 +637,10 @@ class DeviceLatticeBatch(object):
         res = LatticePosteriors(self, log_z, arc_post, node_post, acoustic_scale, lm_scale)
         if B == 0 or self.num_nodes == 0:
             return res
-        L = _native.lib()
-        if not L.asr_lattice_posterior_supported(self.num_nodes, self.num_arcs, self.num_levels):
-            raise NotImplementedError("asr_lattice_posterior_f64: the batch is too large")
-        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
-        chunks = self._utterance_chunks(16, budget)
-        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
-        nbytes = L.asr_lattice_posterior_workspace_bytes(biggest)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
-        head, tail = self._common_args()
-        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
-        for b0, b1 in chunks:
-            self._check(L.asr_lattice_posterior_f64(
-                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(log_z), p(arc_post), p(node_post),
-                p(status), p(ws), nbytes, _native._stream()), 'asr_lattice_posterior_f64')
-        if status.cpu().numpy().any():
-            raise ValueError("asr_lattice_posterior_f64: the batch's index arrays are inconsistent")
+        self.launches = self._launch('asr_lattice_posterior_f64', (), 16, 0, workspace_bytes, (),
+                                     (acoustic_scale, lm_scale), (p(log_z), p(arc_post), p(node_post), p(status)))
+        self._refuse_bad_status(status.cpu().numpy(), 'asr_lattice_posterior_f64')
         return res
 
     # ---- sequence-discriminative training statistics ------------------------------------------
@@ -741,8 +709,7 @@ class DeviceLatticeBatch(object):
             ref = torch.as_tensor(ref)
             if tuple(ref.shape) != (B, T) or ref.dtype.is_floating_point:
                 raise ValueError("ref must be an integer [B, T] = %s tensor, not %s" % ((B, T), tuple(ref.shape)))
-        native = dev.type == 'cuda' and os.environ.get('ASR_LATTICE_TRAIN_NATIVE', '1') != '0'
-        if not native:
+        if not self._native_path('TRAIN'):
             out = self._host_batch().seq_objective(log_probs, ref, criterion, acoustic_scale, lm_scale, boost)
             return tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in out)
         if log_probs.dtype != torch.float32:
@@ -755,28 +722,16 @@ class DeviceLatticeBatch(object):
         self.launches = 0
         if B == 0 or self.num_nodes == 0:
             return objective, arc_grad, occ
-        L = _native.lib()
-        if not L.asr_lattice_seqtrain_supported(self.num_nodes, self.num_arcs, self.num_levels):
-            raise NotImplementedError("asr_lattice_seqtrain_f64: the batch is too large")
         em = self._emission_index(int(T), int(C))
         lp = log_probs.detach().contiguous()
         ref_d = None if ref is None else ref.to(dev, torch.int32).contiguous()
-        budget = int(self.workspace_bytes if workspace_bytes is None else workspace_bytes)
-        chunks = self._utterance_chunks(32, budget)
-        biggest = max(int(self.node_off[b1] - self.node_off[b0]) for b0, b1 in chunks)
-        nbytes = L.asr_lattice_seqtrain_workspace_bytes(biggest)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
-        head, tail = self._common_args()
         il = self.graph.device_arrays(dev)['il']
-        sc = float('nan') if acoustic_scale is None else float(acoustic_scale)
-        for b0, b1 in chunks:
-            self._check(L.asr_lattice_seqtrain_f64(
-                B, b0, b1 - b0, *head, sc, float(lm_scale), *tail, p(il), p(lp), int(T), int(C), p(ref_d),
-                1 if smbr else 0, float(boost), em['E'], em['S'], p(em['em_arc']), p(em['em_ptr']),
-                p(em['em_key']), p(em['em_off']), p(objective), p(arc_grad), p(occ), p(status), p(ws), nbytes,
-                _native._stream()), 'asr_lattice_seqtrain_f64')
-            self.launches += 1
+        self.launches = self._launch(
+            'asr_lattice_seqtrain_f64', (), 32, 0, workspace_bytes, (), (acoustic_scale, lm_scale),
+            (p(il), p(lp), int(T), int(C), p(ref_d), 1 if smbr else 0, float(boost), em['E'], em['S'],
+             p(em['em_arc']), p(em['em_ptr']), p(em['em_key']), p(em['em_off']), p(objective), p(arc_grad), p(occ),
+             p(status)))
         if status.cpu().numpy().any():
             raise ValueError("asr_lattice_seqtrain_f64: the batch's index arrays are inconsistent, or an arc "
                              "reads a frame or class beyond [T, B, C]")

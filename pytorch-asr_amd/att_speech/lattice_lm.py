@@ -50,7 +50,6 @@ epsilons as ordinary arcs (the search may have taken a back-off arc although the
 its LM out under the back-off reading is the usual approximation, as in Kaldi's recipe.
 """
 import ctypes
-import os
 import warnings
 
 import numpy as np
@@ -639,9 +638,8 @@ def rescore_device_batch(batch, lm, label_map=None, scale=1.0, lattice_beam=None
     """DeviceLatticeBatch.rescore_lm (att_speech.lattice_dp): see there"""
     from att_speech.lattice_dp import DeviceLatticeBatch
     graph, B, dev = batch.graph, batch.num_utterances, batch.device
-    native = dev.type == 'cuda' and os.environ.get('ASR_LATTICE_RESCORE_NATIVE', '1') != '0'
     kw = dict(max_frames=batch.max_frames, num_classes=batch.num_classes, workspace_bytes=batch.workspace_bytes)
-    if not native or B == 0 or batch.num_nodes == 0:
+    if not batch._native_path('RESCORE') or B == 0 or batch.num_nodes == 0:
         lats, stats = rescore_lattices(batch.lattices(), lm, label_map, scale, lattice_beam, oov_cost, max_lm_states,
                                        graph=graph)
         blm = BackoffLm.from_fst(lm)

@@ -248,9 +248,12 @@ def test_chunking():
     by_both = check_sweep(batch, pairs, workspace_bytes=12 * int(nodes.max()) + 64)
     assert batch.launches >= 20                         # one pair, and not all utterances, a launch
     assert whole == by_pairs == by_both
+    budget = 16 * int(nodes.max()) + 64
     with quiet():
         a = batch.posteriors(0.5)
-        b = batch.posteriors(0.5, workspace_bytes=16 * int(nodes.max()) + 64)
+        assert batch.launches == 1
+        b = batch.posteriors(0.5, workspace_bytes=budget)
+    assert batch.launches == len(batch._utterance_chunks(16, budget)) > 1
     assert torch.equal(a.arc_log_post, b.arc_log_post) and torch.equal(a.log_z, b.log_z)
     with pytest.raises(ValueError, match='workspace_bytes'):
         batch.best_paths(1.0, workspace_bytes=12 * int(nodes.max()))
@@ -365,8 +368,8 @@ def test_env_switch(monkeypatch):
 
 def test_a_malformed_batch_is_refused():
     """tensors changed behind the constructor's checks: the kernels' own range checks answer.  best_paths never
-    reads out_ptr (it walks the in-arcs only), so that field is posteriors' alone; posteriors does not count
-    its launches, its message is the one raised on the status words the kernel wrote."""
+    reads out_ptr (it walks the in-arcs only), so that field is posteriors' alone.  Both operations count their one
+    launch; the message is the one raised on the status words the kernel wrote."""
     import nbest_cases as NC
     lats, _ = NC.toy_lattices('a', 1.0, 2.0)
     turned = int(np.nonzero(lats[0].src != lats[0].dst)[0][0])
@@ -382,8 +385,7 @@ def test_a_malformed_batch_is_refused():
             getattr(batch, field)[index] = batch.src[index] if value is None else value
             with pytest.raises(ValueError, match=entry + '.*inconsistent'):
                 getattr(batch, op)()
-            if op == 'best_paths':
-                assert batch.launches == 1
+            assert batch.launches == 1
 
 
 def test_the_entry_points_are_exported():
