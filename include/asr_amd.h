@@ -515,8 +515,14 @@ int asr_split_bf16_f32(const float *x, int64_t rows, int64_t cols, int64_t ldx,
  * chan_sums (or null): [2][32] doubles, per output channel the sum and the sum of squares of
  * the bf16 outputs — what the following BatchNorm needs (asr_bn_act_fwd_f32).
  * workspace: asr_conv7x7c32_workspace_bytes() (packed weight fragments / partial sums).
+ * asr_conv7x7c32_supported(B, H, W, stride_h): 1 if all three entry points take the shape, 0
+ * if one of them answers ASR_EINVAL / ASR_EUNSUPPORTED (the launchers run the same checks).
+ * That is stride_h = 3, 7 <= W <= 48 without W = 12, 14, 15 and 20 (the LDS row pitch picked
+ * against bank conflicts overruns the forward kernel's LDS there), H * W < 2^25 (forward) and
+ * B * Ho * Wo < 2^25 (input gradient): 32-bit byte offsets.  (Addition to ABI v24.)
  */
 int64_t asr_conv7x7c32_workspace_bytes(void);
+int asr_conv7x7c32_supported(int B, int H, int W, int stride_h);
 int asr_conv7x7c32_fwd_bf16(const void *x, const float *w, int B, int H, int W, int stride_h,
                             void *y, double *chan_sums, void *workspace, int64_t workspace_bytes,
                             void *stream);
@@ -565,6 +571,13 @@ int asr_conv1_7x7s2_wgrad_bn(const float *x, const void *z, const void *dy, int 
  * same outputs.  Built for cin == 3 and even Fo <= 48 (ASR_EUNSUPPORTED otherwise); workspace
  * asr_conv1c_7x7s2_workspace_bytes(cin).  (ABI v16) */
 int64_t asr_conv1c_7x7s2_workspace_bytes(int cin);
+/* asr_conv1_7x7s2_supported(F, cin): 1 if forward and weight gradient of the first convolution
+ * both take F features of cin channels (the launchers run the same checks; with chan_sums the
+ * forward entry points also need B * ceil((T + 6) / rows) <= 2^17 workgroups, rows = 16 for one
+ * channel and 8 for three).  With Fo = (F - 7) / 2 + 1 that is Fo <= 39 for cin = 1 (F <= 84:
+ * the weight gradient's LDS) and even Fo <= 40 for cin = 3 (F <= 86), 0 for every other cin.
+ * (Addition to ABI v24.) */
+int asr_conv1_7x7s2_supported(int F, int cin);
 int asr_conv1c_7x7s2_fwd(const float *x, const float *w, int B, int T, int F, int cin, void *y,
                          double *chan_sums, void *workspace, int64_t workspace_bytes, void *stream);
 int asr_conv1c_7x7s2_wgrad(const float *x, const void *dy, int B, int T, int F, int cin,

@@ -60,6 +60,8 @@ _SIGNATURES = {
     'asr_sub_rowmax_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'asr_argmax_rows_f32': (_i, [_vp, _i64, _i, _vp, _vp]),
     'asr_conv7x7c32_workspace_bytes': (_i64, []),
+    'asr_conv7x7c32_supported': (_i, [_i, _i, _i, _i]),
+    'asr_conv1_7x7s2_supported': (_i, [_i, _i]),
     'asr_conv7x7c32_fwd_bf16': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     'asr_conv7x7c32_bwd_data_bf16': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     'asr_conv7x7c32_wgrad_bf16': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
@@ -1426,11 +1428,25 @@ def conv7x7c32_wgrad(x, dy, stride_h):
     return dw
 
 
+_INT_MAX = 2 ** 31 - 1
+
+
+def conv7x7c32_supported(B, H, W, stride_h):
+    """asr_conv7x7c32_supported: the shapes all three of asr_conv7x7c32_{fwd,bwd_data,wgrad}_bf16
+    take (the launchers' own checks, so a shape claimed here is never answered with
+    ASR_EUNSUPPORTED in the middle of a training step)"""
+    B, H, W, stride_h = int(B), int(H), int(W), int(stride_h)
+    if not (0 < B <= _INT_MAX and 0 < H <= _INT_MAX and 0 < W <= _INT_MAX and 0 < stride_h <= _INT_MAX):
+        return False
+    return bool(lib().asr_conv7x7c32_supported(B, H, W, stride_h))
+
+
 def conv1_supported(F, cin):
-    """shapes csrc/conv.hip has a first convolution for: one channel (any width up to Fo = 64),
-    or the WSJ recipes' 3 channels with an even output width"""
-    Fo = (F - 7) // 2 + 1
-    return F >= 7 and ((cin == 1 and Fo <= 64) or (cin == 3 and Fo <= 48 and Fo % 2 == 0))
+    """asr_conv1_7x7s2_supported: the widths csrc/conv.hip has a first convolution for, forward
+    and weight gradient both: one channel up to Fo = 39, or the WSJ recipes' 3 channels with an
+    even output width up to Fo = 40"""
+    F, cin = int(F), int(cin)
+    return 7 <= F <= _INT_MAX and cin in (1, 3) and bool(lib().asr_conv1_7x7s2_supported(F, cin))
 
 
 def conv1_fwd(x, weight, want_sums=False):

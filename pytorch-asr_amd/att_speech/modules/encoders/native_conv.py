@@ -11,12 +11,15 @@ from att_speech.modules.encoders import native_bn
 
 
 def supported(conv, x):
-    """the shapes csrc/conv.hip is built for; anything else stays on torch / MIOpen"""
+    """the shapes csrc/conv.hip is built for — as its launchers themselves report them
+    (asr_conv7x7c32_supported: forward, input gradient and weight gradient all take B, H, W);
+    anything else stays on torch / MIOpen"""
     return (x.is_cuda and isinstance(conv, torch.nn.Conv2d) and conv.in_channels == 32
             and conv.out_channels == 32 and tuple(conv.kernel_size) == (7, 7)
             and tuple(conv.stride) == (3, 1) and tuple(conv.padding) == (0, 0)
             and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and x.dim() == 4 and x.size(2) >= 7 and 7 <= x.size(3) <= 48)
+            and x.dim() == 4 and x.size(1) == 32
+            and _native.conv7x7c32_supported(x.size(0), x.size(2), x.size(3), conv.stride[0]))
 
 
 class Conv7x7C32Function(torch.autograd.Function):

@@ -878,7 +878,7 @@ struct Conv1Params {
 };
 
 // window image of input rows t0-6 .. t0-6+nrows-1: [nrows][Fo] x 8 bf16 (a window's 8 samples
-// are four 8-byte loads: 2 fo + 7 <= F - 1 by the definition of Fo; the row index by
+// are four 8-byte loads: 2 fo + 7 <= F - 1 by the definition of Fo for even F; the row index by
 // multiplication: i / Fo = (i * fmagic) >> 20 for i * Fo < 2^20)
 __device__ __forceinline__ void conv1_stage_windows(const Conv1Params &p, int b, int t0, int nrows,
                                                     char *wimg, int tid, int nt) {
@@ -890,9 +890,14 @@ __device__ __forceinline__ void conv1_stage_windows(const Conv1Params &p, int b,
         bf16x8 v = {};
         if (t >= 0 && t < p.T) {
             const float2 *src = reinterpret_cast<const float2 *>(xb + (size_t)t * p.F + 2 * fo);
+            // odd F: the last window's 8th sample lies outside the row — behind the last row, outside
+            // the tensor.  Its weight is zero, but 0 x whatever stands there is NaN if that is not finite
+            const bool whole = 2 * (int)fo + 7 < p.F;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float2 f2 = src[j];
+                float2 f2;
+                if (j < 3 || whole) f2 = src[j];
+                else f2 = float2{reinterpret_cast<const float *>(src)[6], 0.f};
                 v[2 * j] = (__bf16)f2.x;
                 v[2 * j + 1] = (__bf16)f2.y;
             }
@@ -1059,6 +1064,8 @@ __device__ __forceinline__ void conv1_wgrad_body(const Conv1Params &p, const Con
             const unsigned row = (i * fmagic) >> 20, fo = i - row * (unsigned)Fo;
             const int t = t0 - 6 + (int)row;
             const bool ok = (int)i < nwin && t >= 0 && t < p.T;
+            // (odd F: src[3].y of a row's last window is the sample behind the row, see
+            //  conv1_stage_windows; here it only feeds tap column kf = 7, which the reduction drops)
             const float2 *src = reinterpret_cast<const float2 *>(xb + (size_t)(ok ? t : 0) * p.F + 2 * fo);
 #pragma unroll
             for (int j = 0; j < 4; ++j) wreg[u][j] = ok ? src[j] : float2{0.f, 0.f};
@@ -1443,12 +1450,14 @@ extern "C" int64_t asr_conv7x7c32_workspace_bytes(void) {
     return (int64_t)KSTEPS * 64 * 8 * 2 * 2 + (int64_t)WGRAD_WGS * 49 * 1024 * 4 + 256;
 }
 
-extern "C" int asr_conv7x7c32_fwd_bf16(const void *x, const float *w, int B, int H, int W,
-                                       int stride_h, void *y, double *chan_sums, void *workspace,
-                                       int64_t workspace_bytes, void *stream) {
+// ---- shape checks ----------------------------------------------------------------------
+// One static function per launcher: everything about a shape that makes the launcher answer
+// ASR_EINVAL / ASR_EUNSUPPORTED, and the launch geometry that follows from the shape.  The
+// launchers and the exported queries (asr_conv7x7c32_supported, asr_conv1_7x7s2_supported)
+// call the same functions, so what a query claims is what the launcher takes.
+struct ConvFwdPlan { int Ho, Wo, R, pitch; size_t lds; };
+static int conv_fwd_plan(int B, int H, int W, int stride_h, ConvFwdPlan *pl) {
     if (B <= 0 || H < KS || W < KS) return ASR_EINVAL;
-    if (!x || !w || !y || !workspace || workspace_bytes < asr_conv7x7c32_workspace_bytes())
-        return ASR_EINVAL;
     if (stride_h != 1 && stride_h != 3) return ASR_EUNSUPPORTED;
     const int Ho = (H - KS) / stride_h + 1, Wo = W - KS + 1;
     if (Wo > 48) return ASR_EUNSUPPORTED;
@@ -1461,6 +1470,70 @@ extern "C" int asr_conv7x7c32_fwd_bf16(const void *x, const float *w, int B, int
     if (img > (size_t)4 * FWD_MAXQ * 1024) return ASR_EUNSUPPORTED;
     const size_t lds = img + img / 8 + 4 * 4096 + 2048;
     if (lds > 80 * 1024) return ASR_EUNSUPPORTED;
+    pl->Ho = Ho; pl->Wo = Wo; pl->R = R; pl->pitch = pitch; pl->lds = lds;
+    return ASR_OK;
+}
+
+struct ConvDgradPlan { int Ho, Wo, Rq, pitch; size_t lds; };
+static int conv_dgrad_plan(int B, int H, int W, int stride_h, ConvDgradPlan *pl) {
+    if (B <= 0 || H < KS || W < KS) return ASR_EINVAL;
+    if (stride_h != 3) return ASR_EUNSUPPORTED;
+    const int Ho = (H - KS) / stride_h + 1, Wo = W - KS + 1;
+    if (W > 48) return ASR_EUNSUPPORTED;
+    int Rq = DG_PIX / W;
+    if (Rq > 16) Rq = 16;
+    const int pitch = pick_row_pitch((Wo + 12) * PIX, W, 1, Rq * W, DG_NT);
+    // (the image is filled in whole 1 KiB DMA blocks)
+    const size_t img = ((size_t)(Rq + 2) * pitch + 1023) / 1024 * 1024;
+    if ((int64_t)B * Ho * Wo * 64 >= (1ll << 31)) return ASR_EUNSUPPORTED;     // 32-bit buffer offsets
+    // epilogue beside the image: the partial-sum exchange (class 0 of the output image reuses
+    // its first half) + classes 1 and 2
+    const size_t epi = (size_t)DG_NT * 4 * 64 * 16 + (size_t)2 * DG_PIX * CH * 2;
+    const size_t lds = img + epi;
+    if (lds > 80 * 1024 || img > 28 * 1024) return ASR_EUNSUPPORTED;          // (28 DMA slots)
+    pl->Ho = Ho; pl->Wo = Wo; pl->Rq = Rq; pl->pitch = pitch; pl->lds = lds;
+    return ASR_OK;
+}
+
+struct ConvWgradPlan { int Ho, Wo, KW, rows; size_t lds; };
+static int conv_wgrad_plan(int B, int H, int W, int stride_h, ConvWgradPlan *pl) {
+    if (B <= 0 || H < KS || W < KS) return ASR_EINVAL;
+    if (stride_h != 3) return ASR_EUNSUPPORTED;
+    const int Ho = (H - KS) / stride_h + 1, Wo = W - KS + 1;
+    if (Wo > 48) return ASR_EUNSUPPORTED;
+    const int KW = (Wo + 15) / 16;
+    int rows = 8;                                  // output rows per chunk: as many as LDS and
+    size_t lds = 0;                                // the staging registers take
+    for (; rows >= 1; rows >>= 1) {
+        const int xrows = 3 * (rows - 1) + KS;
+        lds = (size_t)(xrows * W + 24) * PIX + (size_t)rows * 16 * KW * PIX;
+        if (lds <= 72 * 1024 && xrows * W * 4 <= NX_MAX * WGRAD_NT && rows * 16 * KW * 4 <= ND_MAX * WGRAD_NT)
+            break;
+    }
+    if (rows < 1) return ASR_EUNSUPPORTED;
+    pl->Ho = Ho; pl->Wo = Wo; pl->KW = KW; pl->rows = rows; pl->lds = lds;
+    return ASR_OK;
+}
+
+extern "C" int asr_conv7x7c32_supported(int B, int H, int W, int stride_h) {
+    ConvFwdPlan f;
+    ConvDgradPlan d;
+    ConvWgradPlan g;
+    return conv_fwd_plan(B, H, W, stride_h, &f) == ASR_OK && conv_dgrad_plan(B, H, W, stride_h, &d) == ASR_OK &&
+           conv_wgrad_plan(B, H, W, stride_h, &g) == ASR_OK;
+}
+
+extern "C" int asr_conv7x7c32_fwd_bf16(const void *x, const float *w, int B, int H, int W,
+                                       int stride_h, void *y, double *chan_sums, void *workspace,
+                                       int64_t workspace_bytes, void *stream) {
+    if (B <= 0 || H < KS || W < KS) return ASR_EINVAL;
+    if (!x || !w || !y || !workspace || workspace_bytes < asr_conv7x7c32_workspace_bytes())
+        return ASR_EINVAL;
+    ConvFwdPlan pl;
+    const int rc = conv_fwd_plan(B, H, W, stride_h, &pl);
+    if (rc != ASR_OK) return rc;
+    const int Ho = pl.Ho, Wo = pl.Wo, R = pl.R, pitch = pl.pitch;
+    const size_t lds = pl.lds;
     hipStream_t s = (hipStream_t)stream;
     __bf16 *wpack = (__bf16 *)workspace;
     hipLaunchKernelGGL(conv_pack_fwd_kernel, dim3((KSTEPS * 64 * 8 + 255) / 256), dim3(256), 0, s, w, wpack);
@@ -1502,20 +1575,11 @@ extern "C" int asr_conv7x7c32_bwd_data_bf16(const void *dy, const float *w, int 
     if (B <= 0 || H < KS || W < KS) return ASR_EINVAL;
     if (!dy || !w || !dx || !workspace || workspace_bytes < asr_conv7x7c32_workspace_bytes())
         return ASR_EINVAL;
-    if (stride_h != 3) return ASR_EUNSUPPORTED;
-    const int Ho = (H - KS) / stride_h + 1, Wo = W - KS + 1;
-    if (W > 48) return ASR_EUNSUPPORTED;
-    int Rq = DG_PIX / W;
-    if (Rq > 16) Rq = 16;
-    const int pitch = pick_row_pitch((Wo + 12) * PIX, W, 1, Rq * W, DG_NT);
-    // (the image is filled in whole 1 KiB DMA blocks)
-    const size_t img = ((size_t)(Rq + 2) * pitch + 1023) / 1024 * 1024;
-    if ((int64_t)B * Ho * Wo * 64 >= (1ll << 31)) return ASR_EUNSUPPORTED;     // 32-bit buffer offsets
-    // epilogue beside the image: the partial-sum exchange (class 0 of the output image reuses
-    // its first half) + classes 1 and 2
-    const size_t epi = (size_t)DG_NT * 4 * 64 * 16 + (size_t)2 * DG_PIX * CH * 2;
-    const size_t lds = img + epi;
-    if (lds > 80 * 1024 || img > 28 * 1024) return ASR_EUNSUPPORTED;          // (28 DMA slots)
+    ConvDgradPlan pl;
+    const int rc = conv_dgrad_plan(B, H, W, stride_h, &pl);
+    if (rc != ASR_OK) return rc;
+    const int Ho = pl.Ho, Wo = pl.Wo, Rq = pl.Rq, pitch = pl.pitch;
+    const size_t lds = pl.lds;
     hipStream_t s = (hipStream_t)stream;
     __bf16 *wpack = (__bf16 *)workspace + (size_t)KSTEPS * 64 * 8;
     hipLaunchKernelGGL(conv_pack_dgrad_kernel, dim3((KSTEPS * 64 * 8 + 255) / 256), dim3(256), 0, s, w, wpack);
@@ -1552,19 +1616,11 @@ extern "C" int asr_conv7x7c32_wgrad_bf16(const void *x, const void *dy, int B, i
     if (B <= 0 || H < KS || W < KS) return ASR_EINVAL;
     if (!x || !dy || !dw || !workspace || workspace_bytes < asr_conv7x7c32_workspace_bytes())
         return ASR_EINVAL;
-    if (stride_h != 3) return ASR_EUNSUPPORTED;
-    const int Ho = (H - KS) / stride_h + 1, Wo = W - KS + 1;
-    if (Wo > 48) return ASR_EUNSUPPORTED;
-    const int KW = (Wo + 15) / 16;
-    int rows = 8;                                  // output rows per chunk: as many as LDS and
-    size_t lds = 0;                                // the staging registers take
-    for (; rows >= 1; rows >>= 1) {
-        const int xrows = 3 * (rows - 1) + KS;
-        lds = (size_t)(xrows * W + 24) * PIX + (size_t)rows * 16 * KW * PIX;
-        if (lds <= 72 * 1024 && xrows * W * 4 <= NX_MAX * WGRAD_NT && rows * 16 * KW * 4 <= ND_MAX * WGRAD_NT)
-            break;
-    }
-    if (rows < 1) return ASR_EUNSUPPORTED;
+    ConvWgradPlan pl;
+    const int rc = conv_wgrad_plan(B, H, W, stride_h, &pl);
+    if (rc != ASR_OK) return rc;
+    const int Ho = pl.Ho, Wo = pl.Wo, KW = pl.KW, rows = pl.rows;
+    const size_t lds = pl.lds;
     hipStream_t s = (hipStream_t)stream;
     ConvWgradParams p;
     p.x = (const __bf16 *)x; p.dy = (const __bf16 *)dy;
@@ -1596,14 +1652,42 @@ static int conv1_shapes(int B, int T, int F, int *To, int *Fo) {
     return ASR_OK;
 }
 
+// the launchers' shape checks, one function each (see conv_fwd_plan); `want_sums`: the channel
+// statistics share the weight gradient's partial-sum area, 64 floats per workgroup
+static int conv1_fwd_check(int B, int T, int F, int want_sums, int *To, int *Fo, size_t *lds) {
+    const int rc = conv1_shapes(B, T, F, To, Fo);
+    if (rc != ASR_OK) return rc;
+    const int64_t wgs = (int64_t)((*To + C1_ROWS - 1) / C1_ROWS) * B;
+    if (want_sums && wgs * 64 * 4 > asr_conv1_7x7s2_workspace_bytes() - 4 * 64 * 8 * 2 - 256)
+        return ASR_EUNSUPPORTED;
+    const int ntiles = (C1_ROWS * *Fo + 31) / 32;
+    *lds = (size_t)(C1_ROWS + 8) * *Fo * 16 + (size_t)ntiles * 32 * CH * 2 + 512 * 4;
+    if (*lds > 64 * 1024) return ASR_EUNSUPPORTED;
+    return ASR_OK;
+}
+
+// bn: the weight gradient that applies the BatchNorm backward itself (asr_conv1_7x7s2_wgrad_bn)
+static int conv1_wgrad_check(int B, int T, int F, int bn, int *To, int *Fo, size_t *lds) {
+    const int rc = conv1_shapes(B, T, F, To, Fo);
+    if (rc != ASR_OK) return rc;
+    *lds = (size_t)(C1_ROWS + 8) * *Fo * 16 + (size_t)C1_ROWS * *Fo * PIX + (bn ? CH * 8 * 4 : 0);
+    if (*lds < 4 * 2 * 1024 * 4) *lds = 4 * 2 * 1024 * 4;          // the final four-wave sum
+    if (*lds > 64 * 1024) return ASR_EUNSUPPORTED;
+    if (bn && !asr_conv1_7x7s2_wgrad_bn_supported(F)) return ASR_EUNSUPPORTED;
+    return ASR_OK;
+}
+
 extern "C" int asr_conv1_7x7s2_fwd(const float *x, const float *w, int B, int T, int F, void *y,
                                    double *chan_sums, void *workspace, int64_t workspace_bytes,
                                    void *stream) {
     int To, Fo;
-    const int rc = conv1_shapes(B, T, F, &To, &Fo);
+    size_t lds;
+    int rc = conv1_shapes(B, T, F, &To, &Fo);
     if (rc != ASR_OK) return rc;
     if (!x || !w || !y || !workspace || workspace_bytes < asr_conv1_7x7s2_workspace_bytes())
         return ASR_EINVAL;
+    rc = conv1_fwd_check(B, T, F, chan_sums != nullptr, &To, &Fo, &lds);
+    if (rc != ASR_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     __bf16 *wpack = (__bf16 *)workspace;
     hipLaunchKernelGGL(conv1_pack_kernel, dim3(8), dim3(256), 0, s, w, wpack);
@@ -1613,11 +1697,6 @@ extern "C" int asr_conv1_7x7s2_fwd(const float *x, const float *w, int B, int T,
     const dim3 grid((To + C1_ROWS - 1) / C1_ROWS, B);
     // the weight gradient's partial-sum area doubles as the statistics' (never live together)
     p.partial = chan_sums ? (float *)((char *)workspace + 4 * 64 * 8 * 2) : nullptr;
-    if (chan_sums && (int64_t)grid.x * grid.y * 64 * 4 > asr_conv1_7x7s2_workspace_bytes() - 4 * 64 * 8 * 2 - 256)
-        return ASR_EUNSUPPORTED;
-    const int ntiles = (C1_ROWS * Fo + 31) / 32;
-    const size_t lds = (size_t)(C1_ROWS + 8) * Fo * 16 + (size_t)ntiles * 32 * CH * 2 + 512 * 4;
-    if (lds > 64 * 1024) return ASR_EUNSUPPORTED;
     hipLaunchKernelGGL(conv1_fwd_kernel, grid, dim3(256), lds, s, p);
     if (chan_sums) {
         hipLaunchKernelGGL(zero_chan_sums_kernel, dim3(1), dim3(64), 0, s, chan_sums);
@@ -1638,24 +1717,23 @@ static int conv1_wgrad_launch(const float *x, const void *dy, int B, int T, int 
                               void *workspace, int64_t workspace_bytes, const Conv1BnParams *bn,
                               void *stream) {
     int To, Fo;
-    const int rc = conv1_shapes(B, T, F, &To, &Fo);
+    size_t lds;
+    int rc = conv1_shapes(B, T, F, &To, &Fo);
     if (rc != ASR_OK) return rc;
     if (!x || !dy || !dw || !workspace || workspace_bytes < asr_conv1_7x7s2_workspace_bytes())
         return ASR_EINVAL;
+    rc = conv1_wgrad_check(B, T, F, bn != nullptr, &To, &Fo, &lds);
+    if (rc != ASR_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     Conv1Params p;
     p.x = x; p.wpack = nullptr; p.y = (__bf16 *)const_cast<void *>(dy);
     p.partial = (float *)((char *)workspace + 4 * 64 * 8 * 2);
     p.B = B; p.T = T; p.F = F; p.To = To; p.Fo = Fo;
-    size_t lds = (size_t)(C1_ROWS + 8) * Fo * 16 + (size_t)C1_ROWS * Fo * PIX + (bn ? CH * 8 * 4 : 0);
-    if (lds < 4 * 2 * 1024 * 4) lds = 4 * 2 * 1024 * 4;            // the final four-wave sum
-    if (lds > 64 * 1024) return ASR_EUNSUPPORTED;
     const int chunks = B * ((To + C1_ROWS - 1) / C1_ROWS);
     const int nwg = chunks < C1_WGS ? chunks : C1_WGS;
     int di, wpt;
     conv1_wgrad_sizes(Fo, &di, &wpt);
     if (bn) {
-        if (!asr_conv1_7x7s2_wgrad_bn_supported(F)) return ASR_EUNSUPPORTED;
         void (*kern)(Conv1Params, Conv1BnParams) = di <= 5 && wpt <= 2 ? conv1_wgrad_bn_kernel<5, 2>
                                                                          : conv1_wgrad_bn_kernel<8, 3>;
         hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, p, *bn);
@@ -1707,35 +1785,75 @@ extern "C" int64_t asr_conv1c_7x7s2_workspace_bytes(int cin) {
     return (int64_t)cin * 4 * 64 * 8 * 2 + (wg > cs ? wg : cs) + 256;
 }
 
+constexpr int C1C_ROWS = 8;       // output rows per chunk of the three-channel kernels
+
+// the launchers' shape checks, one function each (see conv_fwd_plan)
+static int conv1c_fwd_check(int B, int T, int F, int cin, int want_sums, int *To, int *Fo, size_t *lds, int *rpt) {
+    constexpr int ROWS = C1C_ROWS;
+    const int rc = conv1_shapes(B, T, F, To, Fo);
+    if (rc != ASR_OK) return rc;
+    if (cin != 3 || (*Fo & 1)) return ASR_EUNSUPPORTED;
+    if ((int64_t)T * F * cin * 4 * B >= (1ll << 40)) return ASR_EUNSUPPORTED;
+    const int64_t nchunks = (int64_t)B * ((*To + ROWS - 1) / ROWS);
+    if (nchunks >= (1ll << 31)) return ASR_EUNSUPPORTED;
+    if (want_sums && nchunks * 64 * 4 > (int64_t)(1 << 17) * 64 * 4) return ASR_EUNSUPPORTED;
+    const int ntiles = (ROWS * *Fo + 31) / 32;
+    const int FP = (2 * (*Fo - 1) + 8 + 3) & ~3;
+    size_t otail = (size_t)ntiles * 32 * CH * 2 + 512 * 4;
+    if (otail < (size_t)3 * (ROWS + 8) * FP * 2) otail = (size_t)3 * (ROWS + 8) * FP * 2;      // the planes alias it
+    *lds = (size_t)3 * (ROWS + 8) * *Fo * 16 + otail;
+    *rpt = ((ROWS + 8) * F * 3 + 255) / 256;
+    if (*lds > 64 * 1024 || *rpt > 24) return ASR_EUNSUPPORTED;
+    return ASR_OK;
+}
+
+static int conv1c_wgrad_check(int B, int T, int F, int cin, int *To, int *Fo, size_t *lds, int *di, int *rpt) {
+    constexpr int ROWS = C1C_ROWS;
+    const int rc = conv1_shapes(B, T, F, To, Fo);
+    if (rc != ASR_OK) return rc;
+    if (cin != 3 || (*Fo & 1)) return ASR_EUNSUPPORTED;
+    const int FP = (2 * (*Fo - 1) + 8 + 3) & ~3;
+    *lds = (size_t)3 * (ROWS + 8) * *Fo * 16 + (size_t)ROWS * *Fo * PIX + (size_t)3 * (ROWS + 8) * FP * 2;
+    if (*lds < 4 * 1024 * 4) *lds = 4 * 1024 * 4;                  // the final four-wave sums
+    if (*lds > 64 * 1024) return ASR_EUNSUPPORTED;
+    *di = (ROWS * *Fo * 4 + 255) / 256;
+    *rpt = ((ROWS + 8) * F * 3 + 255) / 256;
+    if (*di > 8 || *rpt > 24) return ASR_EUNSUPPORTED;
+    return ASR_OK;
+}
+
+extern "C" int asr_conv1_7x7s2_supported(int F, int cin) {
+    int To, Fo, di, rpt;
+    size_t lds;
+    if (cin == 1)
+        return conv1_fwd_check(1, 1, F, 1, &To, &Fo, &lds) == ASR_OK &&
+               conv1_wgrad_check(1, 1, F, 0, &To, &Fo, &lds) == ASR_OK;
+    return conv1c_fwd_check(1, 1, F, cin, 1, &To, &Fo, &lds, &rpt) == ASR_OK &&
+           conv1c_wgrad_check(1, 1, F, cin, &To, &Fo, &lds, &di, &rpt) == ASR_OK;
+}
+
 extern "C" int asr_conv1c_7x7s2_fwd(const float *x, const float *w, int B, int T, int F, int cin, void *y,
                                     double *chan_sums, void *workspace, int64_t workspace_bytes,
                                     void *stream) {
-    int To, Fo;
-    const int rc = conv1_shapes(B, T, F, &To, &Fo);
+    int To, Fo, rpt;
+    size_t lds;
+    int rc = conv1_shapes(B, T, F, &To, &Fo);
     if (rc != ASR_OK) return rc;
     if (cin != 3 || (Fo & 1)) return ASR_EUNSUPPORTED;
     if (!x || !w || !y || !workspace || workspace_bytes < asr_conv1c_7x7s2_workspace_bytes(cin))
         return ASR_EINVAL;
-    if ((int64_t)T * F * cin * 4 * B >= (1ll << 40)) return ASR_EUNSUPPORTED;
+    rc = conv1c_fwd_check(B, T, F, cin, chan_sums != nullptr, &To, &Fo, &lds, &rpt);
+    if (rc != ASR_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     __bf16 *wpack = (__bf16 *)workspace;
     hipLaunchKernelGGL(conv1c_pack_kernel<3>, dim3(3 * 8), dim3(256), 0, s, w, wpack);
     Conv1Params p;
     p.x = x; p.wpack = wpack; p.y = (__bf16 *)y;
     p.B = B; p.T = T; p.F = F; p.To = To; p.Fo = Fo;
-    constexpr int ROWS = 8;
+    constexpr int ROWS = C1C_ROWS;
     const int64_t nchunks = (int64_t)B * ((To + ROWS - 1) / ROWS);
-    if (nchunks >= (1ll << 31)) return ASR_EUNSUPPORTED;
     const dim3 grid((unsigned)(nchunks < 768 ? nchunks : 768));       // three workgroups per CU (LDS)
     p.partial = chan_sums ? (float *)((char *)workspace + 3 * 4 * 64 * 8 * 2) : nullptr;
-    if (chan_sums && nchunks * 64 * 4 > (int64_t)(1 << 17) * 64 * 4) return ASR_EUNSUPPORTED;
-    const int ntiles = (ROWS * Fo + 31) / 32;
-    const int FP = (2 * (Fo - 1) + 8 + 3) & ~3;
-    size_t otail = (size_t)ntiles * 32 * CH * 2 + 512 * 4;
-    if (otail < (size_t)3 * (ROWS + 8) * FP * 2) otail = (size_t)3 * (ROWS + 8) * FP * 2;      // the planes alias it
-    const size_t lds = (size_t)3 * (ROWS + 8) * Fo * 16 + otail;
-    const int rpt = ((ROWS + 8) * F * 3 + 255) / 256;
-    if (lds > 64 * 1024 || rpt > 24) return ASR_EUNSUPPORTED;
     if (rpt <= 16) hipLaunchKernelGGL((conv1c_fwd_kernel<3, ROWS, 16>), grid, dim3(256), lds, s, p);
     else hipLaunchKernelGGL((conv1c_fwd_kernel<3, ROWS, 24>), grid, dim3(256), lds, s, p);
     if (chan_sums) {
@@ -1748,26 +1866,23 @@ extern "C" int asr_conv1c_7x7s2_fwd(const float *x, const float *w, int B, int T
 extern "C" int asr_conv1c_7x7s2_wgrad(const float *x, const void *dy, int B, int T, int F, int cin,
                                       float *dw, void *workspace, int64_t workspace_bytes,
                                       void *stream) {
-    int To, Fo;
-    const int rc = conv1_shapes(B, T, F, &To, &Fo);
+    int To, Fo, di, rpt;
+    size_t lds;
+    int rc = conv1_shapes(B, T, F, &To, &Fo);
     if (rc != ASR_OK) return rc;
     if (cin != 3 || (Fo & 1)) return ASR_EUNSUPPORTED;
     if (!x || !dy || !dw || !workspace || workspace_bytes < asr_conv1c_7x7s2_workspace_bytes(cin))
         return ASR_EINVAL;
+    rc = conv1c_wgrad_check(B, T, F, cin, &To, &Fo, &lds, &di, &rpt);
+    if (rc != ASR_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    constexpr int ROWS = 8;
+    constexpr int ROWS = C1C_ROWS;
     Conv1Params p;
     p.x = x; p.wpack = nullptr; p.y = (__bf16 *)const_cast<void *>(dy);
     p.partial = (float *)((char *)workspace + 3 * 4 * 64 * 8 * 2);
     p.B = B; p.T = T; p.F = F; p.To = To; p.Fo = Fo;
-    const int FP = (2 * (Fo - 1) + 8 + 3) & ~3;
-    size_t lds = (size_t)3 * (ROWS + 8) * Fo * 16 + (size_t)ROWS * Fo * PIX + (size_t)3 * (ROWS + 8) * FP * 2;
-    if (lds < 4 * 1024 * 4) lds = 4 * 1024 * 4;                    // the final four-wave sums
-    if (lds > 64 * 1024) return ASR_EUNSUPPORTED;
     const int chunks = B * ((To + ROWS - 1) / ROWS);
     const int nwg = chunks < C1_WGS ? chunks : C1_WGS;
-    const int di = (ROWS * Fo * 4 + 255) / 256, rpt = ((ROWS + 8) * F * 3 + 255) / 256;
-    if (di > 8 || rpt > 24) return ASR_EUNSUPPORTED;
     void (*kern)(Conv1Params) = di <= 5 && rpt <= 16 ? conv1c_wgrad_kernel<3, ROWS, 5, 16>
                                                       : conv1c_wgrad_kernel<3, ROWS, 8, 24>;
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, p);
