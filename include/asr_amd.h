@@ -398,8 +398,17 @@ int asr_gru_bidir_bwd_bf16(const float *dy, int dy_shared, const void *whhT_bf16
  * [H, B, C, W] order (out_time_major: the permute(2,0,1,3) of
  * deep_speech_2.py:142-146).  channels_last != 0: x (and a non-time-major out /
  * dy, and dx) are stored [B, H, W, C] — the layout MIOpen's implicit-GEMM
- * convolutions produce and consume (C % 4 == 0 and C/4 must divide 256).  save_mean / save_invstd
- * [C] feed the backward.  conv_bias [C] (or null): the bias of the convolution that
+ * convolutions produce and consume (C % 4 == 0, C <= 1024 and C/4 must divide 256, i.e. C in
+ * {4, 8, ..., 1024}; ASR_EUNSUPPORTED otherwise, and for bf16 x that is not channels-last;
+ * a refusal launches nothing and leaves every output and the workspace alone).  save_mean /
+ * save_invstd [C] feed the backward.
+ * Batch statistics are summed about a per-channel pivot (the channel's first element) in fp32 per
+ * workgroup and in double across workgroups: the error of the variance is that of a centred
+ * evaluation, depth * 2^-23 * (var + maxdev^2) with maxdev the largest |x - mean| of the channel,
+ * whatever |mean| / std is (a folded conv_bias shifts the mean only).
+ * A NaN in x stays NaN in out like nn.Hardtanh(nn.BatchNorm2d(x)): that element with running
+ * statistics, its whole channel (and that channel's save_mean, dx, dgamma) with batch statistics.
+ * Limit: with running statistics the backward's dx is NaN at a NaN x, where torch returns 0.  conv_bias [C] (or null): the bias of the convolution that
  * produced x, added on the fly (x is then the bias-free convolution), so the
  * framework needs neither the broadcast add nor the full-tensor reduction for its
  * gradient; the backward returns that gradient in dconv_bias (may be null).

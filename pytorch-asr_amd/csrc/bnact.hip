@@ -30,14 +30,24 @@ struct BnParams {
     float lo, hi;
 };
 
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float *x, const float *shift, int C, int HW, double *sums) {
+// Hardtanh that lets a NaN through like nn.Hardtanh (fminf / fmaxf return the other operand)
+__device__ __forceinline__ float clamp_act(float y, float lo, float hi) {
+    return y < lo ? lo : (y > hi ? hi : y);
+}
+
+// Batch statistics: sums[c] = { sum (x - pv), sum (x - pv)^2 } about a per-channel pivot pv,
+// the channel's first element (x[0][c][0][0]).  The variance sum(d^2)/n - (sum(d)/n)^2 then
+// loses depth * 2^-23 * (var + (mean - pv)^2) to the fp32 partial sums, whatever the mean;
+// about 0 it would lose depth * 2^-23 * (var + mean^2).  The folded convolution bias shifts
+// the mean only and is added by bn_finalize_kernel.
+__global__ __launch_bounds__(256) void bn_stats_kernel(const float *x, int C, int HW, double *sums) {
     __shared__ float red[64];
     const int c = blockIdx.x, b = blockIdx.y;
     const float *p = x + ((size_t)b * C + c) * HW;
-    const float sh0 = shift ? shift[c] : 0.f;
+    const float pv = x[(size_t)c * HW];
     float s = 0.f, q = 0.f;
     for (int i = threadIdx.x; i < HW; i += 256) {
-        const float v = p[i] + sh0;
+        const float v = p[i] - pv;
         s += v;
         q += v * v;
     }
@@ -51,14 +61,20 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float *x, const flo
 
 // mean / biased variance -> invstd; running statistics as nn.BatchNorm2d in
 // training mode (unbiased variance, momentum)
-__global__ void bn_finalize_kernel(const double *sums, int C, double n, float eps, float momentum,
-                                   float *mean, float *invstd, float *running_mean,
-                                   float *running_var) {
+// pivot[c * pivot_stride] (float or bf16): the pivot the sums were taken about; shift: the
+// folded convolution bias
+__global__ void bn_finalize_kernel(const double *sums, const void *pivot, int pivot_bf16,
+                                   int64_t pivot_stride, const float *shift, int C, double n,
+                                   float eps, float momentum, float *mean, float *invstd,
+                                   float *running_mean, float *running_var) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const double m = sums[2 * c] / n;
-    double var = sums[2 * c + 1] / n - m * m;
+    const double pv = pivot_bf16 ? (double)(float)((const __bf16 *)pivot)[c * pivot_stride]
+                                 : (double)((const float *)pivot)[c * pivot_stride];
+    const double md = sums[2 * c] / n;
+    double var = sums[2 * c + 1] / n - md * md;
     var = var < 0.0 ? 0.0 : var;
+    const double m = pv + md + (shift ? (double)shift[c] : 0.0);
     mean[c] = (float)m;
     invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) {
@@ -104,7 +120,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(BnParams p, OutT *out) 
     const float sc = p.gamma[c] * p.invstd[c];
     const float sh = p.beta[c] - (p.mean[c] - (p.shift ? p.shift[c] : 0.f)) * sc;
     for (int i = threadIdx.x; i < p.HW; i += 256) {
-        const float y = fminf(fmaxf(fmaf(x[i], sc, sh), p.lo), p.hi);
+        const float y = clamp_act(fmaf(x[i], sc, sh), p.lo, p.hi);
         size_t o;
         if (LAYOUT == 0) {
             o = ((size_t)b * p.C + c) * p.HW + i;
@@ -215,12 +231,12 @@ __device__ __forceinline__ void nhwc_block_atomics(const float (&s)[4], const fl
     for (int i = 0; i < 4; ++i) { rs[threadIdx.x][i] = s[i]; rq[threadIdx.x][i] = q[i]; }
     __syncthreads();
     const int CG = C / 4;
-    if ((int)threadIdx.x < C) {
-        const int cg = threadIdx.x >> 2, i = threadIdx.x & 3;
+    for (int c = threadIdx.x; c < C; c += 256) {          // (C up to 1024: four channels a thread)
+        const int cg = c >> 2, i = c & 3;
         float a = 0.f, b = 0.f;
         for (int t = cg; t < 256; t += CG) { a += rs[t][i]; b += rq[t][i]; }
-        atomicAdd(&sums[2 * threadIdx.x], (double)a);
-        atomicAdd(&sums[2 * threadIdx.x + 1], (double)b);
+        atomicAdd(&sums[2 * c], (double)a);
+        atomicAdd(&sums[2 * c + 1], (double)b);
     }
 }
 
@@ -231,11 +247,14 @@ __device__ __forceinline__ void nhwc_block_atomics(const float (&s)[4], const fl
     const int64_t p0 = (int64_t)blockIdx.x * per, p1 = p0 + per < (P_) ? p0 + per : (P_)
 
 template <typename XT>
-__global__ __launch_bounds__(256) void bn_stats_nhwc_kernel(const XT *x, const float *shift, int64_t P, int C, double *sums) {
+__global__ __launch_bounds__(256) void bn_stats_nhwc_kernel(const XT *x, int64_t P, int C, double *sums) {
     NHWC_THREAD_SETUP(P);
-    float sh0[4], s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    float pv[4], s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    {                                                     // the pivots: pixel 0 (see bn_stats_kernel)
+        const F4 v = load4(x + c0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) sh0[i] = shift ? shift[c0 + i] : 0.f;
+        for (int i = 0; i < 4; ++i) pv[i] = v.v[i];
+    }
     // four pixels per trip, all four loads issued before the first add: one 8-byte load in
     // flight per thread kept the pass at 2.4 TB/s (latency-bound); same accumulation order
     int64_t p = p0 + pl;
@@ -247,7 +266,7 @@ __global__ __launch_bounds__(256) void bn_stats_nhwc_kernel(const XT *x, const f
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float t = v[u].v[i] + sh0[i];
+                const float t = v[u].v[i] - pv[i];
                 s[i] += t;
                 q[i] += t * t;
             }
@@ -256,7 +275,7 @@ __global__ __launch_bounds__(256) void bn_stats_nhwc_kernel(const XT *x, const f
         const F4 v = load4(x + p * C + c0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float u = v.v[i] + sh0[i];
+            const float u = v.v[i] - pv[i];
             s[i] += u;
             q[i] += u * u;
         }
@@ -287,7 +306,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_nhwc_kernel(BnParamsN p, OutT 
         const F4 v = load4(px + pix * C + c0);
         F4 y;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) y.v[i] = fminf(fmaxf(fmaf(v.v[i], sc[i], sh[i]), p.lo), p.hi);
+        for (int i = 0; i < 4; ++i) y.v[i] = clamp_act(fmaf(v.v[i], sc[i], sh[i]), p.lo, p.hi);
         if (TM) {
             const size_t o = tm_index(p, pix, c0);
 #pragma unroll
@@ -405,12 +424,12 @@ __device__ __forceinline__ void nhwc_block_atomics8(const float (&s)[8], const f
     for (int i = 0; i < 8; ++i) { rs8[threadIdx.x][i] = s[i]; rq8[threadIdx.x][i] = q[i]; }
     __syncthreads();
     const int CG = C / 8;
-    if ((int)threadIdx.x < C) {
-        const int cg = threadIdx.x >> 3, i = threadIdx.x & 7;
+    for (int c = threadIdx.x; c < C; c += 256) {          // (C up to 1024: four channels a thread)
+        const int cg = c >> 3, i = c & 7;
         float a = 0.f, b = 0.f;
         for (int t = cg; t < 256; t += CG) { a += rs8[t][i]; b += rq8[t][i]; }
-        atomicAdd(&sums[2 * threadIdx.x], (double)a);
-        atomicAdd(&sums[2 * threadIdx.x + 1], (double)b);
+        atomicAdd(&sums[2 * c], (double)a);
+        atomicAdd(&sums[2 * c + 1], (double)b);
     }
 }
 // Work distribution: chunks of 2*PL pixels, grid-strided — the workgroups running at any time
@@ -436,7 +455,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_nhwc8_kernel(BnParamsN p, OutT
     auto one = [&](int64_t pix, const F8 &v) {
         F8 y;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) y.v[i] = fminf(fmaxf(fmaf(v.v[i], sc[i], sh[i]), p.lo), p.hi);
+        for (int i = 0; i < 8; ++i) y.v[i] = clamp_act(fmaf(v.v[i], sc[i], sh[i]), p.lo, p.hi);
         store8(out + pix * C + c0, y);
     };
     for (int64_t pix = (int64_t)blockIdx.x * 2 * PL + pl; pix < pend; pix += cstep) {
@@ -534,7 +553,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_nhwc_tm_kernel(BnParamsN p, Ou
             const F4 v = load4(px + (r0 * W + j) * C + c0);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                tile[row * CW + (c0 + i) * W + w] = fminf(fmaxf(fmaf(v.v[i], sc[i], sh[i]), p.lo), p.hi);
+                tile[row * CW + (c0 + i) * W + w] = clamp_act(fmaf(v.v[i], sc[i], sh[i]), p.lo, p.hi);
         }
         __syncthreads();
         for (int it = threadIdx.x; it < nr * Q; it += 256) {
@@ -660,13 +679,13 @@ extern "C" int asr_bn_act_fwd_f32(const void *x, int x_bf16, const float *conv_b
     } else if (training) {
         hipLaunchKernelGGL(zero_doubles_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s, sums, 2 * C);
         if (channels_last)
-            if (x_bf16) hipLaunchKernelGGL(bn_stats_nhwc_kernel<__bf16>, dim3(nwg), dim3(256), 0, s, (const __bf16 *)x, conv_bias, P, C, sums);
-            else hipLaunchKernelGGL(bn_stats_nhwc_kernel<float>, dim3(nwg), dim3(256), 0, s, (const float *)x, conv_bias, P, C, sums);
+            if (x_bf16) hipLaunchKernelGGL(bn_stats_nhwc_kernel<__bf16>, dim3(nwg), dim3(256), 0, s, (const __bf16 *)x, P, C, sums);
+            else hipLaunchKernelGGL(bn_stats_nhwc_kernel<float>, dim3(nwg), dim3(256), 0, s, (const float *)x, P, C, sums);
         else
-            hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, s, (const float *)x, conv_bias, C, HW, sums);
-        hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, s, sums, C,
-                           (double)B * HW, eps, momentum, save_mean, save_invstd, running_mean,
-                           running_var);
+            hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, s, (const float *)x, C, HW, sums);
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, s, sums, x, x_bf16,
+                           (int64_t)(channels_last ? 1 : HW), conv_bias, C, (double)B * HW, eps, momentum,
+                           save_mean, save_invstd, running_mean, running_var);
     } else {
         hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 63) / 64), dim3(64), 0, s, running_mean,
                            running_var, C, eps, save_mean, save_invstd);
@@ -744,11 +763,11 @@ extern "C" int asr_bn_act_bwd_phase_f32(const void *x, int x_bf16, const float *
     p.x = (const float *)x; p.B = B; p.C = C; p.HW = HW; p.Wd = W; p.gamma = gamma; p.beta = beta;
     p.mean = save_mean; p.invstd = save_invstd; p.shift = conv_bias; p.lo = lo; p.hi = hi;
     const double n = phase == 2 ? n_total : (double)B * HW;
-    if (do_reduce)
-        hipLaunchKernelGGL(zero_doubles_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s, sums, 2 * C);
     if (x_bf16 && !channels_last) return ASR_EUNSUPPORTED;
+    if (channels_last && (C % 4 != 0 || C > 1024 || 256 % (C / 4) != 0)) return ASR_EUNSUPPORTED;
+    if (do_reduce)                                        // (after the gates: a refusal launches nothing)
+        hipLaunchKernelGGL(zero_doubles_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s, sums, 2 * C);
     if (channels_last) {
-        if (C % 4 != 0 || C > 1024 || 256 % (C / 4) != 0) return ASR_EUNSUPPORTED;
         BnParamsN q;
         q.x = x; q.P = (int64_t)B * HW; q.B = B; q.C = C; q.H = H; q.W = W; q.gamma = gamma;
         q.beta = beta; q.mean = save_mean; q.invstd = save_invstd; q.shift = conv_bias; q.lo = lo; q.hi = hi;
