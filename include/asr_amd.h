@@ -1654,6 +1654,49 @@ int asr_lattice_seqtrain_f64(
     const int64_t *em_off, double *out_objective, double *out_arc_grad, float *out_occ, int32_t *out_status,
     void *workspace, int64_t workspace_bytes, void *stream);
 
+/*
+ * Feature front-end: Kaldi filter-bank features, deltas and CMVN from padded waveforms in one launch, the
+ * arithmetic of the recipes' `compute-fbank-feats --use-energy=true --num-mel-bins=80 | add-deltas` and
+ * `apply-cmvn` (egs/wsj/compute_features.sh:17-18), which the reference runs in a Kaldi pipe per DataLoader
+ * worker (att_speech/data/kaldi_dataset.py:194-202).  These entry points are additions: the ABI version stays 24.
+ *
+ * waves: B rows of samples, int16 (waves_int16 = 1) or fp32 (0), row b at waves + b * wave_stride elements, n_max
+ *   readable samples per row (wave_stride >= n_max); wave_lens [B] i32 (device) the samples of every utterance
+ *   (values beyond n_max are read as n_max).  Samples are taken as they are, with no scaling.
+ * Utterance b has T_b = 1 + (N_b - frame_length) / frame_shift frames (0 when N_b < frame_length), at most T_max.
+ *   Frame t, x[i] = wave[t frame_shift + i], i < frame_length:
+ *     x[i] += dither * z[((b T_max + t) 512 + i)] when dither != 0: the draw of asr_gaussian_noise_f32 under
+ *       tag 2 with this seed and iteration (B T_max 512 < 2^34, else ASR_EUNSUPPORTED);
+ *     x -= mean(x);  e = log(max(sum x^2, FLT_EPSILON));
+ *     x[i] -= preemph x[i-1] for i = frame_length-1 .. 1, x[0] -= preemph x[0];  x[i] *= window[i];
+ *     zero-pad to 512, real FFT, P_k = |X_k|^2 for k = 0 .. 255;
+ *     m_j = sum over k in [first_j, end_j) of mel_w[off_j + k - first_j] P_k;  log(max(m_j, FLT_EPSILON)).
+ *   The F = num_mel_bins + use_energy static features are [e, m_0 ..] (energy first) or [m_0 ..].
+ * Tables (device, fp32, built by the host in fp64 and rounded once): window [frame_length]; twiddles [512, 2] =
+ *   (cos, -sin)(2 pi j / 512); mel_idx [num_mel_bins, 3] i32 = (first, end, off) with 0 <= first <= end <= 256;
+ *   mel_w [mel_w_len], 1 <= mel_w_len <= 512: an FFT bin feeds at most two banks (a bank whose range leaves
+ *   the table counts as empty).
+ * Channels C = delta_order + 1: channel c of frame t = sum_j s_c[j] static[clamp(t + j, 0, T_b - 1)] with
+ *   s_1 = [-2 .. 2] / 10 and s_2 = s_1 * s_1 (9 taps); the clamp repeats the utterance's own edge frames.
+ * CMVN: cmvn_offset, cmvn_scale [F C] in the column order [static | delta | delta-delta] (entry c F + f), either
+ *   may be NULL: y = (x - offset) scale.
+ * out [B, T_max, F, C] f32, every entry written: exactly 0 at t >= T_b.  feat_lens [B] i32 (device) = T_b.
+ * fp32 with every sum in a fixed order: two runs give the same bits, and without dither an utterance's rows do not
+ *   depend on B, its position in the batch or T_max.
+ * asr_fbank_supported: padded == 512, 256 < frame_length <= 512, frame_shift >= 1, 1 <= num_mel_bins <= 128,
+ *   0 <= delta_order <= 2, delta_window == 2; otherwise asr_fbank_f32 returns ASR_EUNSUPPORTED.  ASR_EINVAL,
+ *   before anything is launched: null pointers, negative sizes, mel_w_len outside 1 .. 512, wave_stride < n_max, T_max < 1 with B > 0,
+ *   non-positive frame_length, frame_shift or num_mel_bins, a negative delta_order, flags outside {0, 1}.
+ */
+int asr_fbank_supported(int frame_length, int frame_shift, int padded, int num_mel_bins, int delta_order,
+                        int delta_window);
+int asr_fbank_f32(const void *waves, int64_t wave_stride, int n_max, int waves_int16, const int32_t *wave_lens,
+                  int B, int T_max, const float *window, const float *twiddles, const int32_t *mel_idx,
+                  const float *mel_w, int mel_w_len, int frame_length, int frame_shift, int padded,
+                  int num_mel_bins, int use_energy, int delta_order, int delta_window, float preemph,
+                  const float *cmvn_offset, const float *cmvn_scale, float dither, uint64_t seed,
+                  uint64_t iteration, float *out, int32_t *feat_lens, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ _SIGNATURES = {
                                 _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'asr_bn_act_bwd_phase_f32': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _f,
                                       _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, ctypes.c_double, _vp]),
+    'asr_fbank_supported': (_i, [_i] * 6),
+    'asr_fbank_f32': (_i, [_vp, _i64, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f,
+                           _vp, _vp, _f, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp]),
 }
 
 # include/asr_amd_experiments.h: exported only by `make EXPERIMENTS=1` builds; bound when
