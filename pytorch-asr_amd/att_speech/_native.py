@@ -1154,6 +1154,15 @@ def tcn_attention_step(eproj, enc, enc_lens, filt, glob, w_score, b_score, tempe
     return att_new, ctx
 
 
+def _tcn_scan_shapes(what, T, B, L, A, filt, glob, a0, w_score, enc_lens):
+    """filt [L, B, A*Kf], glob [L, B, A], a0 [T, B], w_score [A], enc_lens [B]: the kernels index
+    every operand by the shape of eproj and the L of glob alone"""
+    if (filt.dim() != 3 or tuple(filt.shape[:2]) != (L, B) or filt.shape[2] % A != 0
+            or tuple(glob.shape) != (L, B, A) or tuple(a0.shape) != (T, B) or w_score.numel() != A
+            or enc_lens.numel() != B):
+        raise AssertionError('%s: inconsistent operand shapes' % what)
+
+
 def tcn_attention_scan_fwd(eproj, filt, glob, a0, w_score, b_score, enc_lens, temperature):
     """asr_tcn_attention_scan_fwd_f32 -> every alignment of the training scan [L, B, T]."""
     eproj, a0 = _dev(eproj, torch.float32, 'eproj'), _dev(a0, torch.float32, 'a0')
@@ -1163,6 +1172,9 @@ def tcn_attention_scan_fwd(eproj, filt, glob, a0, w_score, b_score, enc_lens, te
     enc_lens = _dev(enc_lens, torch.int32, 'enc_lens')
     T, B, A = eproj.shape
     L = glob.shape[0]
+    _tcn_scan_shapes('asr_tcn_attention_scan_fwd_f32', T, B, L, A, filt, glob, a0, w_score, enc_lens)
+    if b_score.numel() != 1:
+        raise AssertionError('asr_tcn_attention_scan_fwd_f32: inconsistent operand shapes')
     att = torch.empty((L, B, T), dtype=torch.float32, device=eproj.device)
     check(lib().asr_tcn_attention_scan_fwd_f32(
         _p(eproj), _p(filt), _p(glob), _p(a0), _p(w_score), _p(b_score), float(temperature),
@@ -1181,6 +1193,9 @@ def tcn_attention_scan_bwd(eproj, filt, glob, a0, w_score, enc_lens, temperature
     att, d_att = _dev(att, torch.float32, 'att'), _dev(d_att, torch.float32, 'd_att')
     T, B, A = eproj.shape
     L = glob.shape[0]
+    _tcn_scan_shapes('asr_tcn_attention_scan_bwd_f32', T, B, L, A, filt, glob, a0, w_score, enc_lens)
+    if att.shape != (L, B, T) or d_att.shape != (L, B, T):
+        raise AssertionError('asr_tcn_attention_scan_bwd_f32: inconsistent operand shapes')
     d_eproj = torch.empty_like(eproj)
     d_filt = torch.empty_like(filt)
     d_glob = torch.empty_like(glob)

@@ -441,13 +441,15 @@ GRU_MUTANTS = ('u_is_b_mod_nu', 'len_0_is_empty')
 
 
 def att_gru_step_ref(eproj, encoded, lens, gx_emb, w_ic, w_hh, b_hh, w_rec, w_score, b_score, h0,
-                     beam, dtype=F64, mut=None, tanh_form=None):
+                     beam, dtype=F64, mut=None, tanh_form=None, records=False):
     """One position of AttentionDecoderRNN._step for B = NU * beam hypotheses; hypothesis b reads
     utterance b // beam; a length of 0 or above T' means T' (clamp_len).
       rec = w_rec h0;  a = softmax_t(w_score . tanh(eproj[t, u] + rec) + b_score + pad_t)
       c = sum_t a[t] encoded[t, u];  gi = gx_emb + w_ic c;  gh = w_hh h0 + b_hh
       r = s(gi_r + gh_r)  z = s(gi_z + gh_z)  n = tanh(gi_n + r gh_n)  h = (1 - z) n + z h0
-    eproj [T, NU, A], encoded [T, NU, E], gx_emb [B, 3H], h0 [B, H] -> (att [B, T], states [B, H])"""
+    eproj [T, NU, A], encoded [T, NU, E], gx_emb [B, 3H], h0 [B, H] -> (att [B, T], states [B, H]);
+    with records=True also what the scan saves for its backward pass: contexts [B, E], gates [B, 4H]
+    = (r, z, n, gh_n) and rec [B, A] (tests/attention_scan_referee.py)"""
     c = lambda x: torch.as_tensor(x).to(dtype)  # noqa: E731
     T, NU, A = eproj.shape
     B, H = h0.shape
@@ -467,6 +469,8 @@ def att_gru_step_ref(eproj, encoded, lens, gx_emb, w_ic, w_hh, b_hh, w_rec, w_sc
     r = torch.sigmoid(gi[:, 0] + gh[:, 0])
     z = torch.sigmoid(gi[:, 1] + gh[:, 1])
     n = torch.tanh(gi[:, 2] + r * gh[:, 2])
+    if records:
+        return att, (1 - z) * n + z * h0, ctx, torch.cat((r, z, n, gh[:, 2]), 1), rec
     return att, (1 - z) * n + z * h0
 
 
