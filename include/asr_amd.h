@@ -272,8 +272,9 @@ int asr_lattice_grouped_forward_f32(
  *   gates_bf16 [T,2,B,H,4] bf16 post-activation gates (one 8-byte record i,f,g,o per
  *                      hidden unit), csave [T,2,B,H] f32 cell states: saved by the
  *                      forward pass for the backward pass
- *   dy     [T,B,2,H]   gradient w.r.t. y; dy_shared != 0: [T,B,H], one gradient for
- *                      both directions (BatchRNN sums them, encoder_utils.py:112-117)
+ *   dy     [T,B,2,H]   gradient w.r.t. y; dy_shared = 1: [T,B,H], one gradient for
+ *                      both directions (BatchRNN sums them, encoder_utils.py:112-117);
+ *                      dy_shared is 0 or 1 (ASR_EINVAL otherwise)
  *   dgates_bf16 [T,B,2,4H] bf16: gradient w.r.t. the gate pre-activations
  *                      (= w.r.t. gx); the caller forms dx, dW_ih, dW_hh from it
  *                      with dense GEMMs (bf16 operands, fp32 accumulation)
@@ -327,10 +328,9 @@ int asr_lstm_dgrad_bf16(const void *dgates_bf16, const void *w_ih_bf16, int T, i
  *             weight_ih_l0_reverse stacked)
  *   y         must be NULL when F != H (that variant writes y_bf16 only)
  * Pre-activations are accumulated in fp32 over both products (no bf16 rounding of
- * x·W_ihᵀ).  ASR_EUNSUPPORTED when bit 0 of asr_lstm_fused_supported(B, H, F) is clear
- * (hidden size not one of 64/128/256/320, another input size, persistent path switched
- * off): the caller then uses the GEMM + asr_lstm_bidir_fwd_bf16.  Bits 1 and 2 of the same
- * word describe the two variants of include/asr_amd_experiments.h (not in the default build). */
+ * x·W_ihᵀ).  ASR_EUNSUPPORTED when asr_lstm_fused_supported(B, H, F) returns 0 (hidden
+ * size not one of 64/128/256/320, another input size, persistent path switched off; 1
+ * otherwise): the caller then uses the GEMM + asr_lstm_bidir_fwd_bf16. */
 int asr_lstm_fused_supported(int B, int H, int F);
 int asr_lstm_bidir_fwd_fused_bf16(const void *x_bf16, const void *wih_bf16,
                                   const void *whh_bf16, const int32_t *lens,

@@ -192,24 +192,13 @@ _SIGNATURES = {
                            _vp, _vp, _f, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp]),
 }
 
-# include/asr_amd_experiments.h: exported only by `make EXPERIMENTS=1` builds; bound when
-# present, never required (experiments_built() tells the callers).
-_EXPERIMENT_SIGNATURES = {
-    'asr_lstm_bidir_bwd_fused_bf16': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp,
-                                           _vp, _i64, _vp, _vp]),
-    'asr_lstm_bidir_fwd_fused_sum_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                               _vp, _vp]),
-}
-_experiments = False
-
-
 class NativeLibraryError(RuntimeError):
     pass
 
 
 def lib():
     """Load libasr_amd.so; fail loudly if it has not been built."""
-    global _lib, _experiments
+    global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise NativeLibraryError(
@@ -224,27 +213,8 @@ def lib():
         if handle.asr_abi_version() != ABI_VERSION:
             raise NativeLibraryError("libasr_amd.so ABI %d != expected %d" % (
                 handle.asr_abi_version(), ABI_VERSION))
-        _experiments = all(hasattr(handle, name) for name in _EXPERIMENT_SIGNATURES)
-        if _experiments:
-            for name, (res, args) in _EXPERIMENT_SIGNATURES.items():
-                fn = getattr(handle, name)
-                fn.restype = res
-                fn.argtypes = args
         _lib = handle
     return _lib
-
-
-def experiments_built():
-    """True when libasr_amd.so was built with EXPERIMENTS=1 (include/asr_amd_experiments.h)."""
-    lib()
-    return _experiments
-
-
-def _need_experiments(what):
-    if not experiments_built():
-        raise NotImplementedError(
-            '%s is an experiment (include/asr_amd_experiments.h): rebuild with '
-            '`make -C pytorch-asr_amd/csrc clean all EXPERIMENTS=1`' % what)
 
 
 def check(code, what):
@@ -591,21 +561,16 @@ def lstm_bidir_fwd(gx, whh_bf16, lens, want_y=True):
     return y, ybf, gates, csave
 
 
-def lstm_fused_supported(B, H, backward=False, F=None, dirsum=False):
-    """asr_lstm_fused_supported: can asr_lstm_bidir_fwd_fused_bf16 (bit 0) /
-    asr_lstm_bidir_bwd_fused_bf16 (bit 1) / asr_lstm_bidir_fwd_fused_sum_bf16 (bit 2, `dirsum`)
-    run this (batch, hidden, input size)?"""
+def lstm_fused_supported(B, H, F=None):
+    """asr_lstm_fused_supported: can asr_lstm_bidir_fwd_fused_bf16 run this (batch, hidden,
+    input size)?"""
     F = H if F is None else F
-    if (dirsum or backward) and not experiments_built():
-        return False
-    return bool(lib().asr_lstm_fused_supported(int(B), int(H), int(F)) & (4 if dirsum else 2 if backward else 1))
+    return bool(lib().asr_lstm_fused_supported(int(B), int(H), int(F)) & 1)
 
 
-def lstm_bidir_fwd_fused(x_bf16, wih_bf16, whh_bf16, lens, want_y=True, want_sum=False):
+def lstm_bidir_fwd_fused(x_bf16, wih_bf16, whh_bf16, lens, want_y=True):
     """asr_lstm_bidir_fwd_fused_bf16: x [T,B,F] bf16, wih [2*4H,F] bf16, whh [2,4H,H] bf16
-    -> the outputs of lstm_bidir_fwd, the input projection computed inside the recurrence.
-    want_sum: also xsum [T,B,H] bf16 = ybf[0, 1:T+1] + ybf[1, 1:T+1], written by the recurrence
-    itself (asr_lstm_bidir_fwd_fused_sum_bf16); returned as a fifth value."""
+    -> the outputs of lstm_bidir_fwd, the input projection computed inside the recurrence."""
     x_bf16 = _dev(x_bf16, torch.bfloat16, 'x')
     wih_bf16 = _dev(wih_bf16, torch.bfloat16, 'wih')
     whh_bf16 = _dev(whh_bf16, torch.bfloat16, 'whh')
@@ -622,17 +587,6 @@ def lstm_bidir_fwd_fused(x_bf16, wih_bf16, whh_bf16, lens, want_y=True, want_sum
     csave = torch.empty((T, 2, B, H), dtype=torch.float32, device=dev)
     nbytes = L.asr_lstm_workspace_bytes(B, H)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    if want_sum:
-        _need_experiments('asr_lstm_bidir_fwd_fused_sum_bf16')
-        xsum = torch.empty((T, B, H), dtype=torch.bfloat16, device=dev)
-        check(L.asr_lstm_bidir_fwd_fused_sum_bf16(_p(x_bf16), _p(wih_bf16), _p(whh_bf16), _p(lens), T, B, H, F,
-                                                  _p(y), _p(ybf), _p(gates), _p(csave), _p(xsum), _p(ws), nbytes,
-                                                  _p(_lstm_err_flag(dev)), _stream()),
-              'asr_lstm_bidir_fwd_fused_sum_bf16')
-        if T % 2:           # the middle frame of an odd T: both directions reach it in the first launch
-            m = T // 2
-            torch.add(ybf[0, m + 1], ybf[1, m + 1], out=xsum[m])
-        return y, ybf, gates, csave, xsum
     check(L.asr_lstm_bidir_fwd_fused_bf16(_p(x_bf16), _p(wih_bf16), _p(whh_bf16), _p(lens), T, B, H, F,
                                           _p(y), _p(ybf), _p(gates), _p(csave), _p(ws), nbytes,
                                           _p(_lstm_err_flag(dev)), _stream()),
@@ -707,56 +661,22 @@ def lstm_wgrad(dgates, x_bf16, y_bf16):
     return dw_ih, dw_hh
 
 
-def _dy_mode(dy, planes):
-    if planes:
-        if dy.dim() != 4 or dy.shape[0] != 2:
-            raise ValueError('dy planes must be [2,T,B,H]')
-        return 2, dy.shape[1], dy.shape[2]
-    return int(dy.dim() == 3), dy.shape[0], dy.shape[1]
-
-
-def lstm_bidir_bwd(dy, whhT_bf16, lens, gates, csave, planes=False):
+def lstm_bidir_bwd(dy, whhT_bf16, lens, gates, csave):
     """asr_lstm_bidir_bwd_bf16 -> dgates [T,B,2,4H] bf16.  dy [T,B,2,H], or [T,B,H] when
-    the two directions share one gradient (their outputs are summed), or with `planes`
-    [2,T,B,H]: that shared gradient as the sum of two planes (lstm_bidir_bwd_fused's dx)."""
+    the two directions share one gradient (their outputs are summed)."""
     dy = _dev(dy, torch.float32, 'dy')
     whhT_bf16 = _dev(whhT_bf16, torch.bfloat16, 'whhT')
     lens = _dev(lens, torch.int32, 'lens')
-    mode, T, B = _dy_mode(dy, planes)
-    H = dy.shape[-1]
+    T, B, H = dy.shape[0], dy.shape[1], dy.shape[-1]
     L = lib()
     dgates = torch.empty((T, B, 2, 4 * H), dtype=torch.bfloat16, device=dy.device)
     nbytes = L.asr_lstm_workspace_bytes(B, H)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
-    check(L.asr_lstm_bidir_bwd_bf16(_p(dy), mode, _p(whhT_bf16), _p(lens), T, B, H,
+    check(L.asr_lstm_bidir_bwd_bf16(_p(dy), int(dy.dim() == 3), _p(whhT_bf16), _p(lens), T, B, H,
                                     _p(gates), _p(csave), _p(dgates), _p(ws), nbytes,
                                     _p(_lstm_err_flag(dy.device)), _stream()),
           'asr_lstm_bidir_bwd_bf16')
     return dgates
-
-
-def lstm_bidir_bwd_fused(dy, whhT_bf16, wihT_bf16, lens, gates, csave, planes=False):
-    """asr_lstm_bidir_bwd_fused_bf16 -> (dgates [T,B,2,4H] bf16, dx [2,T,B,H] f32 planes whose
-    sum is the layer's input gradient).  whhT, wihT: [2,H,4H] bf16; dy as in lstm_bidir_bwd."""
-    dy = _dev(dy, torch.float32, 'dy')
-    whhT_bf16 = _dev(whhT_bf16, torch.bfloat16, 'whhT')
-    wihT_bf16 = _dev(wihT_bf16, torch.bfloat16, 'wihT')
-    lens = _dev(lens, torch.int32, 'lens')
-    _need_experiments('asr_lstm_bidir_bwd_fused_bf16')
-    mode, T, B = _dy_mode(dy, planes)
-    H = dy.shape[-1]
-    if tuple(wihT_bf16.shape) != (2, H, 4 * H) or tuple(whhT_bf16.shape) != (2, H, 4 * H):
-        raise ValueError('lstm_bidir_bwd_fused: the layer input size must equal the hidden size')
-    L = lib()
-    dgates = torch.empty((T, B, 2, 4 * H), dtype=torch.bfloat16, device=dy.device)
-    dx = torch.empty((2, T, B, H), dtype=torch.float32, device=dy.device)
-    nbytes = L.asr_lstm_workspace_bytes(B, H)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
-    check(L.asr_lstm_bidir_bwd_fused_bf16(_p(dy), mode, _p(whhT_bf16), _p(wihT_bf16), _p(lens), T, B, H,
-                                          _p(gates), _p(csave), _p(dgates), _p(dx), _p(ws), nbytes,
-                                          _p(_lstm_err_flag(dy.device)), _stream()),
-          'asr_lstm_bidir_bwd_fused_bf16')
-    return dgates, dx
 
 
 def gru_supported(B, H):

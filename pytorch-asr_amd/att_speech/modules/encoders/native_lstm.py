@@ -35,7 +35,7 @@ def _fused_fits(T, B, H, F):
             and T * B * F * 2 < _FUSED_LIMITS['input'])
 
 
-def _forward_layer(xb, w_ih, whh, lens_dev, T, B, H, want_y, want_sum=False):
+def _forward_layer(xb, w_ih, whh, lens_dev, T, B, H, want_y):
     """One layer's recurrence from its bf16 input [T*B, F].  Where the library has the fused
     kernel (F == H; or H = 320, F = 352 when the fp32 outputs are not wanted) the input
     projection runs inside the persistent recurrence (asr_lstm_bidir_fwd_fused_bf16: no
@@ -47,14 +47,6 @@ def _forward_layer(xb, w_ih, whh, lens_dev, T, B, H, want_y, want_sum=False):
     mode = os.environ.get('ASR_LSTM_FUSED', '1')         # 0: never, inner: only F == H layers
     if (mode != '0' and (F == H or (not want_y and mode != 'inner'))
             and _native.lstm_fused_supported(B, H, F=F) and _fused_fits(T, B, H, F)):
-        # want_sum + ASR_LSTM_DIRSUM=1: the direction sum on the bf16 planes comes out of the
-        # recurrence itself (a fifth return value).  Opt-in: measured break-even at B=768 — the
-        # second launch's set-up and the per-step tile fetch cost what the saved pass over the
-        # planes (0.1 ms per layer) gains.
-        if (want_sum and T >= 2 and os.environ.get('ASR_LSTM_DIRSUM', '0') == '1'
-                and _native.lstm_fused_supported(B, H, F=F, dirsum=True)):
-            return _native.lstm_bidir_fwd_fused(xb.view(T, B, F), w_ih, whh, lens_dev, want_y=want_y,
-                                                want_sum=True)
         return _native.lstm_bidir_fwd_fused(xb.view(T, B, F), w_ih, whh, lens_dev, want_y=want_y)
     if os.environ.get('ASR_GX_FP32', '0') == '1':
         gx = _mm_f32(xb, w_ih.t()).view(T, B, 2, 4 * H)
@@ -196,11 +188,10 @@ class BiLSTMStackFunction(torch.autograd.Function):
             w_ih, whh = w_ihs[l], whhs[l]
             H = whh.shape[2]
             last = l == n - 1
-            out = _forward_layer(xb, w_ih, whh, lens_dev, T, B, H, last, want_sum=not last)
-            y, ybf, gates, csave = out[:4]
+            y, ybf, gates, csave = _forward_layer(xb, w_ih, whh, lens_dev, T, B, H, last)
             saved += [xb, w_ih, whh, ybf, gates, csave]
             if not last:
-                xb = (out[4] if len(out) > 4 else ybf[0, 1:T + 1] + ybf[1, 1:T + 1]).view(T * B, H)
+                xb = (ybf[0, 1:T + 1] + ybf[1, 1:T + 1]).view(T * B, H)
         ctx.save_for_backward(lens_dev, *saved)
         ctx.n = n
         return y.sum(2)
@@ -209,31 +200,17 @@ class BiLSTMStackFunction(torch.autograd.Function):
     def backward(ctx, dy):
         lens_dev, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         grads = [None] * (4 * ctx.n)
-        dy, planes = dy.contiguous(), False
-        # opt-in: measured slower than recurrence + GEMM at the bench shape (csrc/lstm.hip,
-        # lstm_bwd_dx_kernel)
-        fuse_ok = os.environ.get('ASR_LSTM_FUSED_BWD', '0') == '1'
+        dy = dy.contiguous()
         for l in range(ctx.n - 1, -1, -1):
             xb, w_ih, whh, ybf, gates, csave = saved[6 * l:6 * l + 6]
             _, T2, B, H = ybf.shape
             T, F = T2 - 2, xb.shape[1]
             whhT = whh.transpose(1, 2).contiguous()
             need_dx = l > 0 or ctx.needs_input_grad[0]
-            if need_dx and l > 0 and F == H and fuse_ok and _native.lstm_fused_supported(B, H, backward=True):
-                # the input gradient comes out of the recurrence (one plane per direction) and
-                # goes into the layer below as it is: no [T*B, 8H] x [8H, F] GEMM
-                dgb, dy_next = _native.lstm_bidir_bwd_fused(
-                    dy, whhT, w_ih.view(2, 4 * H, F).transpose(1, 2).contiguous(), lens_dev,
-                    gates, csave, planes=planes)
-                planes_next = True
-            else:
-                dgb = _native.lstm_bidir_bwd(dy, whhT, lens_dev, gates, csave, planes=planes)
-                dy_next, planes_next = None, False
-                if need_dx:
-                    dy_next = _input_gradient(dgb, w_ih, T, B, H, F, bf16_out=l == 0 and ctx.x_bf16)
+            dgb = _native.lstm_bidir_bwd(dy, whhT, lens_dev, gates, csave)
+            dy = _input_gradient(dgb, w_ih, T, B, H, F, bf16_out=l == 0 and ctx.x_bf16) if need_dx else None
             dw_ih, dw_hh = _weight_gradients(dgb, xb, ybf, T, B, H, F)
             grads[4 * l:4 * l + 4] = [dw_ih[:4 * H], dw_hh[0], dw_ih[4 * H:], dw_hh[1]]
-            dy, planes = dy_next, planes_next
         return (dy if ctx.needs_input_grad[0] else None, None) + tuple(grads)
 
 

@@ -122,12 +122,6 @@ struct LstmFwdParams {
     u32x2 *gates;           // [T,2,B,H] records of 4 bf16 post-activation gates (saved for backward)
     float *csave;           // [T,2,B,H] cell state after the step
     int step;
-    // persistent kernel: steps [s_begin, s_end) of the T (a launch that starts past step 0
-    // picks its state up from hbuf / csave, the team counters keep counting).  xsum [T,B,H]
-    // bf16 != null: every step also writes bf16(h_own) + the OTHER direction's bf16 output of
-    // its frame — valid when that direction wrote the frame in an EARLIER launch.
-    int s_begin, s_end;
-    __bf16 *xsum;
 };
 
 // K-loop of one wave: acc += A[32 x 16*KS] * B[16*KS x 32] with both operands
@@ -135,29 +129,27 @@ struct LstmFwdParams {
 // compile time the loop is fully unrolled and every fragment load is issued
 // before the first MFMA, so the L2 latency is paid once, not per k-step.
 
-// grid: x = hidden tile (H/32), y = batch tile group (ceil(Bp/(32*BT))), z = direction
+// grid: x = hidden tile (H/32), y = batch tile (ceil(B/32)), z = direction
 #ifdef ASR_LSTM_STAMPS
 #define STAMP(i) stamp[i] = __builtin_amdgcn_s_memtime()
 #else
 #define STAMP(i) do {} while (0)
 #endif
 
-// One time step of the forward recurrence for a [32*BT batch] x [32 hidden]
+// One time step of the forward recurrence for a [32 batch] x [32 hidden]
 // tile (all four gates).  KS = H/16 k-steps (compile time).  Wave g owns gate
 // g: its W_hh fragments (KS x 16 B per lane) are loaded straight to registers,
 // the h_{t-1} tile — needed by all four waves — is staged once through LDS.
-// BT = 2 halves the W_hh re-reads per step (the kernel is bound by operand
-// fetch from L2 / Infinity Cache, not by the MFMAs).
-template <int KS, int BT, int GXB>
+template <int KS, int GXB>
 __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(LstmFwdParams p) {
 #ifdef ASR_LSTM_STAMPS
     unsigned long long stamp[4];
     const unsigned long long stamp_start = __builtin_amdgcn_s_memtime();
 #endif
-    __shared__ __attribute__((aligned(16))) __bf16 a_lds[BT * KS * 512];
-    __shared__ float g_lds[BT][4][32][33];
+    __shared__ __attribute__((aligned(16))) __bf16 a_lds[KS * 512];
+    __shared__ float g_lds[4][32][33];
     const int H = p.H, B = p.B;
-    const int j0 = blockIdx.x * 32, b0 = blockIdx.y * 32 * BT, dir = blockIdx.z;
+    const int j0 = blockIdx.x * 32, b0 = blockIdx.y * 32, dir = blockIdx.z;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int t = dir == 0 ? p.step : p.T - 1 - p.step;
     const int Bp = (B + 63) & ~63;
@@ -173,12 +165,12 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(LstmFwdParams p) {
 #pragma unroll
         for (int k = 0; k < KS; ++k) fb[k] = *reinterpret_cast<const bf16x8 *>(bp + k * 512);
     }
-    // ---- h_{t-1} tile(s): BT*KS KiB, contiguous in fragment-major order
+    // ---- h_{t-1} tile: KS KiB, contiguous in fragment-major order
     {
         const bf16x8 *src = reinterpret_cast<const bf16x8 *>(
-            hprev + (size_t)blockIdx.y * BT * KS * 512);
+            hprev + (size_t)blockIdx.y * KS * 512);
         bf16x8 *dst = reinterpret_cast<bf16x8 *>(a_lds);
-        constexpr int CH = BT * KS * 64;            // 16-byte chunks
+        constexpr int CH = KS * 64;                 // 16-byte chunks
         bf16x8 tmp[(CH + 255) / 256];
 #pragma unroll
         for (int i = 0; i < (CH + 255) / 256; ++i) {
@@ -194,7 +186,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(LstmFwdParams p) {
     STAMP(0);
 
     // ---- operands of the pointwise phase: issued now, consumed after the GEMM
-    constexpr int NE = 4 * BT;
+    constexpr int NE = 4;
     float pgx[NE][4], pc[NE];
     bool pact[NE];
 #pragma unroll
@@ -212,38 +204,30 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(LstmFwdParams p) {
 
     // ---- gate pre-activation tiles
     {
-        f32x16 acc[BT];
+        f32x16 acc;
 #pragma unroll
-        for (int bt = 0; bt < BT; ++bt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[bt][i] = 0.f;
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         const bf16x8 *al = reinterpret_cast<const bf16x8 *>(a_lds) + lane;
 #pragma unroll
         for (int k = 0; k < KS; ++k)
-#pragma unroll
-            for (int bt = 0; bt < BT; ++bt)
-                acc[bt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[(bt * KS + k) * 64], fb[k],
-                                                                  acc[bt], 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[k * 64], fb[k], acc, 0, 0, 0);
         STAMP(1);
         const int col = lane & 31;
 #pragma unroll
-        for (int bt = 0; bt < BT; ++bt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-                g_lds[bt][wave][row][col] = acc[bt][i];
-            }
+        for (int i = 0; i < 16; ++i) {
+            const int row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+            g_lds[wave][row][col] = acc[i];
+        }
     }
     __syncthreads();
     STAMP(2);
 
-    // ---- pointwise cell update: BT*1024 (b, j) elements over 256 threads
+    // ---- pointwise cell update: 1024 (b, j) elements over 256 threads
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         const int idx = e * 256 + threadIdx.x;
-        const int rowg = idx >> 5, col = idx & 31;
-        const int bt = rowg >> 5, row = rowg & 31;
-        const int b = b0 + rowg, j = j0 + col;
+        const int row = idx >> 5, col = idx & 31;
+        const int b = b0 + row, j = j0 + col;
         if (b < B) {
             const size_t sidx = ((size_t)dir * B + b) * H + j;
             float *yo = p.y + (((size_t)t * B + b) * 2 + dir) * H + j;
@@ -252,7 +236,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(LstmFwdParams p) {
             if (pact[e]) {
                 float pre[4], gt[4], c, h;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) pre[g] = g_lds[bt][g][row][col] + pgx[e][g];
+                for (int g = 0; g < 4; ++g) pre[g] = g_lds[g][row][col] + pgx[e][g];
                 lstm_cell_fwd(pre, pc[e], gt, c, h);
                 p.cbuf[sidx] = c;
                 hnext[frag_off(b, j, KS)] = (__bf16)h;
@@ -281,12 +265,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(LstmFwdParams p) {
 
 struct LstmBwdParams {
     const float *dy;        // [T,B,2,H] gradient w.r.t. the per-direction outputs, or [T,B,H]
-    int dy_shared;          // 1: one gradient for both directions (the directions are summed);
-                            // 2: that gradient as the sum of two planes [2][T,B,H] (the `dx`
-                            //    planes of the layer above; persistent kernels only)
-    const __bf16 *wihT;     // fused input gradient (lstm_bwd_dx_kernel, F == H): fragment-major pack
-                            // of W_ihᵀ [2 dir][H rows (input feature)][4H cols]
-    float *dx;              // ... output [2 dir][T,B,H]: dgates_dir · W_ih_dir per direction
+    int dy_shared;          // 1: one gradient for both directions (the directions are summed)
     const __bf16 *whhT;     // fragment-major pack of W_hhᵀ: [2 dir][H rows][4H cols]
     const int32_t *lens;
     int T, B, H;
@@ -298,15 +277,15 @@ struct LstmBwdParams {
     int step;
 };
 
-// One time step of the backward recurrence for a [32*BT batch] x [32 hidden]
+// One time step of the backward recurrence for a [32 batch] x [32 hidden]
 // tile: dh_rec[b][j] = sum_k dgates_prev[b][k] * W_hh[k][j] with K = 4H split
 // over the four waves (wave w takes the columns of gate w), then the LSTM cell
 // backward in fp32.
-template <int KS, int BT>
+template <int KS>
 __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(LstmBwdParams p) {
-    __shared__ float part[BT][4][32][33];
+    __shared__ float part[4][32][33];
     const int H = p.H, B = p.B, H4 = 4 * p.H;
-    const int j0 = blockIdx.x * 32, b0 = blockIdx.y * 32 * BT, dir = blockIdx.z;
+    const int j0 = blockIdx.x * 32, b0 = blockIdx.y * 32, dir = blockIdx.z;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // the backward scan visits frames in the opposite order of the forward one
     const int t = dir == 0 ? p.T - 1 - p.step : p.step;
@@ -315,25 +294,20 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(LstmBwdParams p) {
     const __bf16 *dgprev = p.dgbuf + ((size_t)(p.step & 1) * 2 + dir) * Bp * H4;
     __bf16 *dgnext = p.dgbuf + ((size_t)((p.step + 1) & 1) * 2 + dir) * Bp * H4;
 
-    // ---- operands: W_hhᵀ slice of this wave (registers) and the dgates tiles
-    bf16x8 fb[KS], fa[BT][KS];
+    // ---- operands: W_hhᵀ slice of this wave (registers) and the dgates tile
+    bf16x8 fb[KS], fa[KS];
     {
         const __bf16 *bp = p.whhT + (size_t)dir * H * H4 +
                            (((size_t)blockIdx.x * KS4 + (size_t)wave * KS) * 64 + lane) * 8;
 #pragma unroll
         for (int k = 0; k < KS; ++k) fb[k] = *reinterpret_cast<const bf16x8 *>(bp + k * 512);
+        const __bf16 *ap = dgprev + (((size_t)blockIdx.y * KS4 + (size_t)wave * KS) * 64 + lane) * 8;
 #pragma unroll
-        for (int bt = 0; bt < BT; ++bt) {
-            const __bf16 *ap = dgprev + ((((size_t)blockIdx.y * BT + bt) * KS4 +
-                                          (size_t)wave * KS) * 64 + lane) * 8;
-#pragma unroll
-            for (int k = 0; k < KS; ++k)
-                fa[bt][k] = *reinterpret_cast<const bf16x8 *>(ap + k * 512);
-        }
+        for (int k = 0; k < KS; ++k) fa[k] = *reinterpret_cast<const bf16x8 *>(ap + k * 512);
     }
 
     // ---- operands of the pointwise phase: issued now, consumed after the GEMM
-    constexpr int NE = 4 * BT;
+    constexpr int NE = 4;
     float pg[NE][4], pcs[NE], pcp[NE], pdy[NE], pdc[NE];
     bool pact[NE];
 #pragma unroll
@@ -355,19 +329,16 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(LstmBwdParams p) {
 
     {
         const int col = lane & 31;
+        f32x16 acc;
 #pragma unroll
-        for (int bt = 0; bt < BT; ++bt) {
-            f32x16 acc;
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int k = 0; k < KS; ++k)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[k], fb[k], acc, 0, 0, 0);
 #pragma unroll
-            for (int k = 0; k < KS; ++k)
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[bt][k], fb[k], acc, 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-                part[bt][wave][row][col] = acc[i];
-            }
+        for (int i = 0; i < 16; ++i) {
+            const int row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+            part[wave][row][col] = acc[i];
         }
     }
     __syncthreads();
@@ -375,15 +346,14 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(LstmBwdParams p) {
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         const int idx = e * 256 + threadIdx.x;
-        const int rowg = idx >> 5, col = idx & 31;
-        const int bt = rowg >> 5, row = rowg & 31;
-        const int b = b0 + rowg, j = j0 + col;
+        const int row = idx >> 5, col = idx & 31;
+        const int b = b0 + row, j = j0 + col;
         if (b < B) {
             const size_t sidx = ((size_t)dir * B + b) * H + j;
             __bf16 *dgo = p.dgates + (((size_t)t * B + b) * 2 + dir) * H4 + j;
             if (pact[e]) {
-                const float dh = pdy[e] + (part[bt][0][row][col] + part[bt][1][row][col]) +
-                                 (part[bt][2][row][col] + part[bt][3][row][col]);
+                const float dh = pdy[e] + (part[0][row][col] + part[1][row][col]) +
+                                 (part[2][row][col] + part[3][row][col]);
                 float d[4], dcout;
                 lstm_cell_bwd(pg[e], pcs[e], pcp[e], dh, pdc[e], d, dcout);   // pcp: cell state the step started from
                 const float d_i = d[0], d_f = d[1], d_g = d[2], d_o = d[3];
@@ -465,29 +435,6 @@ __device__ __forceinline__ void dma16_sc1(rsrc_words r, unsigned lds_byte, unsig
                  : "s"(lds_byte), "v"(voff), "s"(r), "s"(soff)
                  : "memory");
 }
-// four of them, 1 KiB apart on BOTH sides (the instruction offset moves the LDS and the
-// global address alike): one M0 set-up for four k-steps of a fragment-major tile
-__device__ __forceinline__ void dma16x4_sc1(rsrc_words r, unsigned lds_byte, unsigned voff, unsigned soff) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen sc1 lds\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen offset:1024 sc1 lds\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen offset:2048 sc1 lds\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen offset:3072 sc1 lds\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_byte), "v"(voff), "s"(r), "s"(soff)
-                 : "memory");
-}
-// 64 lanes x 4 bytes
-__device__ __forceinline__ void dma4_s(rsrc_words r, unsigned lds_byte, unsigned voff, unsigned soff) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dword %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_byte), "v"(voff), "s"(r), "s"(soff)
-                 : "memory");
-}
 __device__ __forceinline__ unsigned lds_addr(const void *ptr) {
     return (unsigned)(size_t)((__attribute__((address_space(3))) const void *)ptr);
 }
@@ -506,16 +453,13 @@ __device__ __forceinline__ unsigned lds_addr(const void *ptr) {
 // workgroup waits for the team's counter and waves 0-3 while the hand-off tile is in
 // flight: both windows (911 / 1036 cycles at B=512) were idle.  The sum x_t·W_ih + h·W_hh
 // is accumulated in fp32 in one MFMA chain (the bf16 rounding of `gx` is gone).
-// SUM: the launch also writes p.xsum (see LstmFwdParams) — its own instantiation, so that the
-// other launches keep their register allocation (the XF kernels sit at 247-256 VGPRs)
-template <int KS, int NE, int GXB, int XF, int SUM = 0>
+template <int KS, int NE, int GXB, int XF>
 __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, LstmTeamCtl ctl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __bf16 *a_lds = reinterpret_cast<__bf16 *>(smem);                       // KS KiB
     float (*g_lds)[32][65] = reinterpret_cast<float (*)[32][65]>(smem + KS * 1024);
     __bf16 *h_lds = reinterpret_cast<__bf16 *>(smem + KS * 1024 + ASR_GLDS_BYTES);   // 4 KiB
     __bf16 *x_lds = reinterpret_cast<__bf16 *>(smem + KS * 1024 + ASR_GLDS_BYTES + 4096);   // XF KiB
-    __bf16 *o_lds = reinterpret_cast<__bf16 *>(smem + KS * 1024 + ASR_GLDS_BYTES + 4096 + XF * 1024);   // 2 x 4 KiB (SUM)
     constexpr int KX = XF > 0 ? XF : 1;
     __shared__ int dead_s;
     const int H = p.H, B = p.B, T = p.T;
@@ -605,11 +549,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
         const int xr = lane & 31, b = b0 + xr < B ? b0 + xr : B - 1;
         if (xr < 8 * NE) vx = (u32)(b * (16 * KX) + 16 * wv + 8 * (lane >> 5)) * 2u;
     }
-    const int S0 = p.s_begin, S1 = p.s_end;
-    constexpr bool summ = XF && SUM;
-    const rsrc_words ybD = raw_rsrc(p.ybf, summ ? (unsigned)((u32)(2 * (T + 2)) * fyb) : 0u);
-    const __amdgpu_buffer_rsrc_t xsR = __builtin_amdgcn_make_buffer_rsrc(
-        p.xsum, 0, summ ? (int)((u32)T * fyb) : 0, 0x00020000);
     auto x_dma = [&](int tq) {
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -617,23 +556,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
                 dma16_s(xD, (unsigned)__builtin_amdgcn_readfirstlane(
                                 (int)(lds_addr(x_lds) + (unsigned)(wave + 8 * i) * 1024u)),
                         vx + (u32)i * 256u, (u32)__builtin_amdgcn_readfirstlane((int)((u32)tq * fx_frame)));
-    };
-    // SUM: the other direction's bf16 outputs of frame tq (written by an earlier launch), rows
-    // 8 wave .. + 7 of the tile x this workgroup's 64 columns: 1 KiB per wave 0..3, lane = (row,
-    // 16-byte chunk), into buffer `par` of o_lds.  Fetched one step ahead like x: these bytes come
-    // from HBM, and a DMA issued with the hand-off tile put their 2 us on every step's
-    // critical path (measured: 4.65 instead of 3.9 us per step).
-    auto o_dma = [&](int tq, int par) {
-        if (wave < 4) {
-            int ln = lane;      // (an opaque copy: hoisted out of the loop these offsets cost registers)
-            asm volatile("" : "+v"(ln));
-            const int orow = 8 * wv + (ln >> 3);
-            const u32 vo = orow < 8 * NE && b0 + orow < B
-                               ? (u32)(((b0 + orow) * H + j0) * 2 + (ln & 7) * 16) : 0x80000000u;
-            dma16_s(ybD, (unsigned)__builtin_amdgcn_readfirstlane(
-                             (int)(lds_addr(o_lds) + (unsigned)par * 4096u + (unsigned)wv * 1024u)), vo,
-                    (u32)__builtin_amdgcn_readfirstlane((int)((u32)((1 - dir) * (T + 2) + tq + 1) * fyb)));
-        }
     };
     // y == null: zero records, every fp32 output store is dropped by the bounds check
     const __amdgpu_buffer_rsrc_t yR = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y ? (int)((u32)T * fy) : 0, 0x00020000);
@@ -652,35 +574,12 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
     // (behind the hand-off tile in the wave's in-order vmcnt queue, never in
     // front of the team poll); the outputs nobody inside the launch reads are
     // stored after the team signal, under the hand-off latency.
-    if (S0 > 0) {
-        // pick the state up where the previous launch left it: c_{t-1} from csave, this
-        // workgroup's own part of h_{t-1} from the hand-off buffer (the same bytes h_lds held)
-        const int tp = dir == 0 ? S0 - 1 : T - S0;
-#pragma unroll
-        for (int e = 0; e < NE; ++e)
-            c[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                csR, inb[e] ? l4 : OOBV, (u32)tp * fcs + scs[e], 0));
-        __syncthreads();                // the zero fill of h_lds above
-        if (tid < 256) {
-            const unsigned off = (unsigned)(((((size_t)(S0 & 1) * 2 + dir) * Bp * H) +
-                                             ((size_t)btile * KS + 4 * jt + (tid >> 6)) * 512 + (tid & 63) * 8) * 2);
-            reinterpret_cast<u32x4 *>(h_lds)[tid] = __builtin_amdgcn_raw_buffer_load_b128(
-                hres, (tid & 31) < 8 * NE ? off : 0xFFFFFFFFu, 0, ASR_SC1);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const int row = e * 8 + wave;
-            hq[e] = h_lds[(((col >> 4) * 64) + row + 32 * ((col >> 3) & 1)) * 8 + (col & 7)];
-        }
-    }
     float pgx[XF ? 1 : NE][4];
     {
-        const int t0 = dir == 0 ? S0 : T - 1 - S0;
+        const int t0 = dir == 0 ? 0 : T - 1;
         if constexpr (XF) {
             __syncthreads();            // the zero fill above
             x_dma(t0);
-            if constexpr (summ) o_dma(t0, S0 & 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         } else {
@@ -707,7 +606,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
     float soh[NE] = {}, sc[NE] = {};
     __bf16 shq[NE] = {};                 // NOY: the bf16 output of the step (0 on padding frames)
     bool sact[NE] = {};
-    int st = 0, st_par = 0;
+    int st = 0;
     // live == false (the first step has nothing to store yet): every offset out of range,
     // so the call has the same VMEM count on every step (counted vmcnt waits around it)
     auto bulk_store = [&](bool live) {
@@ -727,22 +626,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
                                                   on && sact[e] ? l4 * 2u : OOBV, ust * fg + scs[e] * 2u, 0);
         }
     };
-    // SUM: own output + the other direction's (buffer st_par of o_lds), issued BEHIND the team
-    // signal: its LDS reads would otherwise sit between the hand-off store and the signal
-    auto sum_store = [&]() {
-        const u32 ust = (u32)st;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const bool on = inb[e];
-            int cl = col;
-            asm volatile("" : "+v"(cl));
-            const __bf16 xs = (__bf16)((float)shq[e] + (float)o_lds[st_par * 2048 + (e * 8 + wave) * 64 + cl]);
-            __builtin_amdgcn_raw_buffer_store_b16(
-                (short)__builtin_bit_cast(unsigned short, xs), xsR, on ? l2 : OOBV,
-                ust * fyb + (u32)__builtin_amdgcn_readfirstlane(((b0 + e * 8 + wv) * H + j0) * 2), 0);
-        }
-    };
-
     if constexpr (XF) {
         // Everything the prologue loaded must have landed BEFORE the loop: the compiler does
         // not see the LDS-DMA inside the asm, so a wait it places inside the loop for one of
@@ -760,7 +643,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
         for (int e = 0; e < NE; ++e) asm volatile("" : "+v"(len[e]));
     }
     PSTAMP_DECL;
-    for (int step = S0; step < S1; ++step) {
+    for (int step = 0; step < T; ++step) {
         const int t = dir == 0 ? step : T - 1 - step;
         if constexpr (XF) if (wave >= 4) x_mfma();          // under the team wait
         if (step > 0 && tid == 0 && !dead_s) {
@@ -829,7 +712,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
                 // (32-row tiles keep two weight fragments in scratch; their reloads inside the
                 // MFMA loop would wait for this DMA: issued behind the loop there)
                 if constexpr (NE < 4) x_dma(tn);
-                if constexpr (summ) o_dma(tn, (step + 1) & 1);      // (read in the cell phase of step + 1)
             } else {
 #pragma unroll
                 for (int e = 0; e < NE; ++e)
@@ -862,7 +744,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
         PSTAMP(2);
         const bool dead = dead_s != 0;
         st = t;
-        st_par = step & 1;
         auto cell_one = [&](int e) {
             const int row = e * 8 + wave;
             if (sact[e]) {
@@ -932,7 +813,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_kernel(LstmFwdParams p, 
         __syncthreads();
         PSTAMP(4);
         if (tid == 0) __hip_atomic_fetch_add(myctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (summ) sum_store();
         if constexpr (!XF) {
 #pragma unroll
             for (int e = 0; e < NE; ++e)
@@ -1017,22 +897,19 @@ __global__ __launch_bounds__(512) void lstm_bwd_persist_kernel(LstmBwdParams p, 
     }
     const u32 fg = (u32)B * 2u * H * 8u, fcs = (u32)B * 2u * H * 4u;
     const u32 fdy = (u32)B * H * 4u * (p.dy_shared ? 1u : 2u), fdg = (u32)B * 2u * H4 * 2u;
-    // dy_shared == 2: the second plane lies T frames further on; otherwise that load is out
-    // of range and returns 0
-    const u32 dy2 = p.dy_shared == 2 ? (u32)T * fdy : 0x80000000u;
     const __amdgpu_buffer_rsrc_t gR = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<u32x2 *>(p.gates), 0, (int)((u32)T * fg), 0x00020000);
     const __amdgpu_buffer_rsrc_t csR = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(p.csave), 0, (int)((u32)T * fcs), 0x00020000);
     const __amdgpu_buffer_rsrc_t dyR = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(p.dy), 0,
-        __builtin_amdgcn_readfirstlane((int)((u32)T * fdy * (p.dy_shared == 2 ? 2u : 1u))), 0x00020000);
+        __builtin_amdgcn_readfirstlane((int)((u32)T * fdy)), 0x00020000);
     const __amdgpu_buffer_rsrc_t dgR = __builtin_amdgcn_make_buffer_rsrc(
         p.dgates, 0, (int)((u32)T * fdg), 0x00020000);
     auto ldf = [&](__amdgpu_buffer_rsrc_t R, u32 voff, u32 soff) -> float {
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(R, voff, soff, 0));
     };
-    struct Pre { u32x2 g[NE]; float cp[NE], dy[NE], dyb[NE]; };     // gates stay packed until used
+    struct Pre { u32x2 g[NE]; float cp[NE], dy[NE]; };     // gates stay packed until used
     auto fetch = [&](int t, Pre &q) {
         const int tp = dir == 0 ? t - 1 : t + 1;
         const int tpc = tp < 0 ? 0 : (tp >= T ? T - 1 : tp);
@@ -1041,7 +918,6 @@ __global__ __launch_bounds__(512) void lstm_bwd_persist_kernel(LstmBwdParams p, 
             q.g[e] = __builtin_amdgcn_raw_buffer_load_b64(gR, vcs[e] * 2u, (u32)t * fg, 0);
             q.cp[e] = ldf(csR, vcs[e], (u32)tpc * fcs);
             q.dy[e] = ldf(dyR, vdy[e], (u32)t * fdy);
-            q.dyb[e] = ldf(dyR, vdy[e], (u32)t * fdy + dy2);
         }
     };
     Pre cur;
@@ -1139,7 +1015,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_persist_kernel(LstmBwdParams p, 
             const int row = e * 8 + wave;
             float od[4];
             if (t < len[e]) {
-                const float dh = (cur.dy[e] + cur.dyb[e]) + (part[0][row][col] + part[1][row][col]) +
+                const float dh = cur.dy[e] + (part[0][row][col] + part[1][row][col]) +
                                  (part[2][row][col] + part[3][row][col]);
                 const float cp = (tp >= 0 && tp < len[e]) ? cur.cp[e] : 0.f;
                 float dcout, gt[4];
@@ -1187,342 +1063,6 @@ __global__ __launch_bounds__(512) void lstm_bwd_persist_kernel(LstmBwdParams p, 
 #endif
 }
 
-// Backward recurrence WITH the input gradient: dx_t = dgates_t · W_ih per direction
-// (replaces the [T·B, 8H] x [8H, F] library GEMM behind asr_lstm_bidir_bwd_bf16 when F == H).
-// MEASURED SLOWER than recurrence + GEMM at the bench shape (B=576, H=320: 1669 us against
-// 1246 + 331): unlike the forward kernel, whose hand-off waits were idle, every phase of the
-// backward step is bound by what a wave has to ISSUE, so the dx product (+800 cycles per
-// step beyond the team wait it overlaps), the partial-sum read-out (+500) and the operand
-// DMAs (+700) all add to the step (ablation stamps).  Callers opt in
-// (att_speech: ASR_LSTM_FUSED_BWD=1); the parity tests run it either way.
-// Same team protocol, tiles and arithmetic as lstm_bwd_persist_kernel; what differs:
-//  * the team's dgates tile of step s stays in a_lds until the tile of step s+1 replaces it,
-//    so every wave multiplies it with its W_ihᵀ slice (registers, next to the W_hhᵀ slice) at
-//    the top of step s+2 — in the window in which the workgroup waits for the team counter
-//    anyway; the four K-quarter partials meet in `part` (free between the cell phase and the
-//    next dh product) and leave as one coalesced fp32 row per wave.  The two directions write
-//    separate planes; the layer below reads both (dy_shared == 2);
-//  * two weight slices take 160 of the 256 VGPRs, so nothing else may be staged in registers:
-//    the hand-off tile comes global -> LDS by LDS-DMA (the buffer is fragment-major, 1 KiB
-//    per k-step, lane-linear on both sides), and so do the pointwise operands of the next
-//    step (saved gates, neighbour cell state, dy): issued behind the team signal, landed
-//    under the dx product, read from LDS in the cell phase;
-//  * every per-row quantity (lengths, row offsets) is wave-uniform and lives in SGPRs.
-template <int KS, int NE>
-__global__ __launch_bounds__(512) void lstm_bwd_dx_kernel(LstmBwdParams p, LstmTeamCtl ctl) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int KS4 = 4 * KS, RL = 8 * NE;
-    __bf16 *a_lds = reinterpret_cast<__bf16 *>(smem);                       // 4*KS KiB
-    float (*part)[32][65] = reinterpret_cast<float (*)[32][65]>(smem + KS4 * 1024);
-    __bf16 *dg_lds = reinterpret_cast<__bf16 *>(smem + KS4 * 1024 + ASR_GLDS_BYTES);   // 16 KiB
-    unsigned char *pre = smem + KS4 * 1024 + ASR_GLDS_BYTES + 16384;
-    u32x2 (*pg)[64] = reinterpret_cast<u32x2 (*)[64]>(pre);                 // [RL][64] gate records
-    float (*pcp)[64] = reinterpret_cast<float (*)[64]>(pre + RL * 512);     // [RL][64] neighbour c
-    float (*pdy)[64] = reinterpret_cast<float (*)[64]>(pre + RL * 768);     // [2][RL][64] dy planes
-    __shared__ int dead_s;
-    typedef unsigned int u32;
-    constexpr u32 OOBV = 0x80000000u;
-    const int H = p.H, B = p.B, T = p.T, H4 = 4 * p.H;
-    int jt = blockIdx.x, btile = blockIdx.y + ctl.bt0, dir = blockIdx.z;
-    if (ctl.xcd_teams) {                     // XCD-affine 1-D grid, as in lstm_bwd_persist_kernel
-        const int slot = blockIdx.x >> 3, team = (slot / (p.H / 64)) * 8 + (blockIdx.x & 7);
-        if (team >= ctl.xcd_teams) return;
-        jt = slot % (p.H / 64);
-        btile = (team >> 1) + ctl.bt0;
-        dir = team & 1;
-    }
-    const int j0 = jt * 64, b0 = btile * RL, njt = H / 64;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kq = wave >> 1, js = wave & 1;
-    const size_t Bp = ctl.rows;
-    unsigned *myctr = ctl.ctr + ((size_t)dir * ctl.nbt + btile) * 32;
-    if (tid == 0) dead_s = 0;
-    for (int i = tid; i < 8192; i += 512) dg_lds[i] = (__bf16)0.f;      // padding rows stay 0
-    for (int i = tid; i < KS4 * 64; i += 512)
-        reinterpret_cast<u32x4 *>(a_lds)[i] = u32x4{0u, 0u, 0u, 0u};
-
-    bf16x8 fb[KS], fxb[KS];
-    {
-        const size_t wo = (size_t)dir * H * H4 +
-                          (((size_t)(2 * jt + js) * KS4 + (size_t)kq * KS) * 64 + lane) * 8;
-#pragma unroll
-        for (int k = 0; k < KS; ++k) fb[k] = *reinterpret_cast<const bf16x8 *>(p.whhT + wo + k * 512);
-#pragma unroll
-        for (int k = 0; k < KS; ++k) fxb[k] = *reinterpret_cast<const bf16x8 *>(p.wihT + wo + k * 512);
-    }
-    const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc(
-        p.dgbuf, 0, (int)(2 * 2 * Bp * H4 * 2), 0x00020000);
-    const rsrc_words dresD = raw_rsrc(p.dgbuf, (unsigned)(2 * 2 * Bp * H4 * 2));
-
-    // rows of this wave: b = b0 + e*8 + wave (wave-uniform: SGPRs)
-    const int col = lane;
-    int len[NE], bc[NE];
-    bool inb[NE];
-    float dcarry[NE], pcs[NE];
-#pragma unroll
-    for (int e = 0; e < NE; ++e) {
-        const int b = b0 + e * 8 + wave;
-        inb[e] = b < B;
-        bc[e] = b < B ? b : B - 1;
-        len[e] = __builtin_amdgcn_readfirstlane(b < B ? p.lens[bc[e]] : 0);
-        dcarry[e] = 0.f;
-    }
-    const u32 l4 = (u32)lane * 4u, l2 = (u32)lane * 2u;
-    const u32 fg = (u32)B * 2u * H * 8u, fcs = (u32)B * 2u * H * 4u;
-    const u32 fdy = (u32)B * H * 4u * (p.dy_shared ? 1u : 2u), fdg = (u32)B * 2u * H4 * 2u;
-    const u32 fdx = (u32)B * H * 4u;
-    const rsrc_words gD = raw_rsrc(p.gates, (u32)T * fg);
-    const rsrc_words csD = raw_rsrc(p.csave, (u32)T * fcs);
-    const rsrc_words dyD = raw_rsrc(p.dy, (u32)T * fdy * (p.dy_shared == 2 ? 2u : 1u));
-    const __amdgpu_buffer_rsrc_t dgR = __builtin_amdgcn_make_buffer_rsrc(
-        p.dgates, 0, (int)((u32)T * fdg), 0x00020000);
-    const __amdgpu_buffer_rsrc_t dxR = __builtin_amdgcn_make_buffer_rsrc(
-        p.dx, 0, (int)(2u * (u32)T * fdx), 0x00020000);
-
-    // pointwise operands of frame t (all RL rows of the tile) -> LDS: 5*RL/4 LDS-DMAs of
-    // 1 KiB (two rows of gate records, or four rows of c / dy), dealt round-robin to the
-    // waves; the per-lane source offsets are loop-invariant
-    constexpr int NQ = 5 * RL / 4, NQW = (NQ + 7) / 8;
-    u32 pvo[NQW];
-#pragma unroll
-    for (int i = 0; i < NQW; ++i) {
-        const int q = wave + 8 * i;
-        if (q < RL / 2) {
-            const int r = 2 * q + (lane >> 5), b = b0 + r < B ? b0 + r : B - 1;
-            pvo[i] = (u32)((dir * B + b) * H + j0) * 8u + (u32)(lane & 31) * 16u;
-        } else {
-            const int qq = q < 3 * RL / 4 ? q - RL / 2 : (q < RL ? q - 3 * RL / 4 : q - RL);
-            const int r = 4 * qq + (lane >> 4), b = b0 + r < B ? b0 + r : B - 1;
-            if (q < 3 * RL / 4) pvo[i] = (u32)((dir * B + b) * H + j0) * 4u + (u32)(lane & 15) * 16u;
-            else pvo[i] = (u32)(p.dy_shared ? b * H + j0 : (b * 2 + dir) * H + j0) * 4u + (u32)(lane & 15) * 16u;
-            if (q >= RL && p.dy_shared != 2) pvo[i] = OOBV;      // no second dy plane: zeros
-        }
-    }
-    auto pre_dma = [&](int t) {
-        const int tp = dir == 0 ? t - 1 : t + 1;
-        const int tpc = tp < 0 ? 0 : (tp >= T ? T - 1 : tp);
-#pragma unroll
-        for (int i = 0; i < NQW; ++i) {
-            const int q = wave + 8 * i;
-            if (q < RL / 2) dma16_s(gD, lds_addr(pre) + (unsigned)q * 1024u, pvo[i], (u32)t * fg);
-            else if (q < 3 * RL / 4) dma16_s(csD, lds_addr(pre) + (unsigned)q * 1024u, pvo[i], (u32)tpc * fcs);
-            else if (q < RL) dma16_s(dyD, lds_addr(pre) + (unsigned)q * 1024u, pvo[i], (u32)t * fdy);
-            else if (q < NQ) dma16_s(dyD, lds_addr(pre) + (unsigned)q * 1024u, pvo[i], (u32)(T + t) * fdy);
-        }
-    };
-    __bf16 sod[NE][4] = {};
-    int st = 0;
-    auto bulk_store = [&](bool live) {
-#pragma unroll
-        for (int e = 0; e < NE; ++e)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                __builtin_amdgcn_raw_buffer_store_b16(
-                    (short)__builtin_bit_cast(unsigned short, sod[e][g]), dgR,
-                    live && inb[e] ? l2 : OOBV,
-                    (u32)st * fdg + (u32)(((b0 + e * 8 + wave) * 2 + dir) * H4 + g * H + j0) * 2u, 0);
-    };
-    // a_lds (the dgates of one step, all 4H columns) x this wave's W_ihᵀ slice -> part
-    auto dx_mfma = [&]() {
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        const bf16x8 *al = reinterpret_cast<const bf16x8 *>(a_lds) + (size_t)kq * KS * 64 + lane;
-        acc = mfma_chain<0, KS, 2>(al, fxb, acc);
-        const int c32 = lane & 31;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-            part[kq][row][js * 32 + c32] = acc[i];
-        }
-    };
-    // the four K-quarter partials in `part` -> dx[dir][frame of step sq]
-    auto dx_store = [&](bool live, int sq) {
-        const int tq = live ? (dir == 0 ? T - 1 - sq : sq) : 0;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const int row = e * 8 + wave;
-            const float v = (part[0][row][col] + part[1][row][col]) + (part[2][row][col] + part[3][row][col]);
-            __builtin_amdgcn_raw_buffer_store_b32(
-                __builtin_bit_cast(int, v), dxR, live && inb[e] ? l4 : OOBV,
-                (u32)(dir * T + tq) * fdx + (u32)((b0 + e * 8 + wave) * H + j0) * 4u, 0);
-        }
-    };
-    // the other workgroups' 4*(KS-4) k-steps of the team's dgates tile, (KS-4)/2 per wave
-    auto tile_dma = [&](int step) {
-        const unsigned base = (unsigned)((((size_t)(step & 1) * 2 + dir) * Bp * H4 +
-                                          (size_t)btile * KS4 * 512) * 2);
-        const u32 voff = (lane & 31) < RL ? (u32)lane * 16u : OOBV;
-        if constexpr (KS > 4) {
-            // a wave's k-steps come in runs of four consecutive ones when (KS-4)/2 % 4 == 0
-            // (the gap left by this workgroup's own k-steps starts at a multiple of four)
-            constexpr int PW = (KS - 4) / 2, GR = PW % 4 == 0 ? 4 : 1;
-#pragma unroll
-            for (int i = 0; i < PW; i += GR) {
-                const int ko = wave * PW + i, g = ko / (KS - 4), r = ko - g * (KS - 4);
-                const int k = g * KS + (r < 4 * jt ? r : r + 4);
-                if constexpr (GR == 4)
-                    dma16x4_sc1(dresD, lds_addr(a_lds) + (unsigned)k * 1024u, voff, base + (unsigned)k * 1024u);
-                else
-                    dma16_sc1(dresD, lds_addr(a_lds) + (unsigned)k * 1024u, voff, base + (unsigned)k * 1024u);
-            }
-        }
-    };
-    auto own_copy = [&]() {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = i * 512 + tid, bi = c >> 6;         // bi = gate * 4 + kk
-            reinterpret_cast<u32x4 *>(a_lds)[((bi >> 2) * KS + 4 * jt + (bi & 3)) * 64 + (c & 63)] =
-                reinterpret_cast<const u32x4 *>(dg_lds)[c];
-        }
-    };
-    {
-        const int t0 = dir == 0 ? T - 1 : 0;
-#pragma unroll
-        for (int e = 0; e < NE; ++e)
-            pcs[e] = p.csave[(((size_t)t0 * 2 + dir) * B + bc[e]) * H + j0 + col];
-    }
-    const bool last_q = wave + 8 * (NQW - 1) < NQ;      // does this wave issue NQW operand DMAs, or one less
-    // everything loaded so far lands before the loop: the compiler cannot count the LDS-DMA
-    // inside the asm (see lstm_fwd_persist_kernel)
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-        asm volatile("" : "+v"(fb[k]));
-        asm volatile("" : "+v"(fxb[k]));
-    }
-#pragma unroll
-    for (int e = 0; e < NE; ++e) asm volatile("" : "+v"(pcs[e]));
-
-    PSTAMP_DECL;
-    for (int step = 0; step < T; ++step) {
-        const int t = dir == 0 ? T - 1 - step : step;
-        // The team counter is looked at before and in the middle of the dx product (a_lds still
-        // holds the dgates of step - 2, loaded for the dh product of step - 1): the round trip
-        // of the poll runs under the MFMAs instead of after them
-        const unsigned target = (unsigned)(njt * step);
-        const bool poller = step > 0 && tid == 0 && !dead_s;
-        unsigned seen = 0;
-        if (poller) seen = __hip_atomic_load(myctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (step >= 2) {
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            const bf16x8 *al = reinterpret_cast<const bf16x8 *>(a_lds) + (size_t)kq * KS * 64 + lane;
-            acc = mfma_chain<0, KS / 2, 2>(al, fxb, acc);
-            if (poller && seen < target)
-                seen = __hip_atomic_load(myctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            acc = mfma_chain<KS / 2, KS, 2>(al, fxb, acc);
-            const int c32 = lane & 31;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-                part[kq][row][js * 32 + c32] = acc[i];
-            }
-        }
-        if (poller && seen < target) {
-            if (!team_wait(myctr, target, ctl.spin_limit, ctl.err)) dead_s = 1;
-        }
-        PSTAMP(0);
-        __syncthreads();
-        tile_dma(step);
-        bulk_store(step > 0);     // previous step's dgates rows, under the tile's flight
-        own_copy();
-        dx_store(step >= 2, step - 2);
-        pre_dma(t);               // this step's pointwise operands: needed two barriers further on
-        // the tile has landed once all but the stores and operand DMAs behind it are done
-        // (VMEM retires in issue order)
-        if (last_q) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(5 * NE + NQW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(5 * NE + NQW - 1) : "memory");
-        __syncthreads();
-        PSTAMP(1);
-        {
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            const bf16x8 *al = reinterpret_cast<const bf16x8 *>(a_lds) + (size_t)kq * KS * 64 + lane;
-            acc = mfma_chain<0, KS, 2>(al, fb, acc);
-            const int c32 = lane & 31;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-                part[kq][row][js * 32 + c32] = acc[i];
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the operand DMAs
-        __syncthreads();
-        PSTAMP(2);
-        const bool dead = dead_s != 0;
-        st = t;
-        const int tp = dir == 0 ? t - 1 : t + 1;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const int row = e * 8 + wave;
-            float od[4];
-            const float cpn = pcp[row][col];
-            if (t < len[e]) {
-                const float dh = (pdy[row][col] + pdy[RL + row][col]) +
-                                 (part[0][row][col] + part[1][row][col]) +
-                                 (part[2][row][col] + part[3][row][col]);
-                const float cp = (tp >= 0 && tp < len[e]) ? cpn : 0.f;
-                float dcout, gt[4];
-                unpack_gates(pg[row][col], gt);
-                lstm_cell_bwd(gt, pcs[e], cp, dh, dcarry[e], od, dcout);
-                dcarry[e] = dcout;
-                if (dead) od[0] = od[1] = od[2] = od[3] = __builtin_nanf("");
-            } else {
-                od[0] = od[1] = od[2] = od[3] = 0.f;
-                dcarry[e] = 0.f;
-            }
-            const int slot = ((col >> 4) * 64 + row + 32 * ((col >> 3) & 1)) * 8 + (col & 7);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                sod[e][g] = (__bf16)od[g];
-                dg_lds[g * 2048 + slot] = sod[e][g];
-            }
-            pcs[e] = cpn;               // c of the frame the next step visits
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int bi = wave * 2 + r, g = bi >> 2, kk = bi & 3;
-            const u32x4 v = reinterpret_cast<const u32x4 *>(dg_lds)[bi * 64 + lane];
-            const unsigned off = (unsigned)(((((size_t)((step + 1) & 1) * 2 + dir) * Bp * H4) +
-                                             ((size_t)btile * KS4 + g * KS + 4 * jt + kk) * 512 + lane * 8) * 2);
-            __builtin_amdgcn_raw_buffer_store_b128(v, dres, (lane & 31) < RL ? off : 0xFFFFFFFFu,
-                                                   0, ASR_SC1);
-        }
-        PSTAMP(3);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        PSTAMP(4);
-        if (tid == 0) __hip_atomic_fetch_add(myctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        PSTAMP(5);
-    }
-    bulk_store(true);                     // the last step's dgates rows
-    // dx of the last two steps: step T-2's tile is in a_lds, step T-1's comes with one more
-    // hand-off round
-    if (T >= 2) dx_mfma();
-    if (tid == 0 && !dead_s) {
-        if (!team_wait(myctr, (unsigned)(njt * T), ctl.spin_limit, ctl.err)) dead_s = 1;
-    }
-    __syncthreads();
-    tile_dma(T);
-    own_copy();
-    dx_store(T >= 2, T - 2);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NE) : "memory");
-    __syncthreads();
-    dx_mfma();
-    __syncthreads();
-    dx_store(true, T - 1);
-#ifdef ASR_LSTM_STAMPS
-    __syncthreads();
-    if (tid == 0 && b0 < B)
-        for (int i = 0; i < 6; ++i)
-            p.dgates[(((size_t)0 * B + b0) * 2 + dir) * H4 + j0 + i] = (__bf16)((float)pst[i] / T / 16.f);
-#endif
-}
-
 }  // namespace
 
 extern "C" int64_t asr_lstm_workspace_bytes(int B, int H) {
@@ -1539,7 +1079,7 @@ extern "C" int64_t asr_lstm_workspace_bytes(int B, int H) {
 namespace {
 int lstm_fwd_impl(const void *gx, int gx_bf16, const void *x_bf16, const void *wih_bf16, int F,
                   const void *whh_bf16, const int32_t *lens, int T, int B, int H,
-                  float *y, void *y_bf16, void *gates_bf16, float *csave, void *xsum_bf16,
+                  float *y, void *y_bf16, void *gates_bf16, float *csave,
                   void *workspace, int64_t workspace_bytes, uint32_t *err_flag, void *stream);
 }
 
@@ -1551,7 +1091,7 @@ extern "C" int asr_lstm_bidir_fwd_bf16(const void *gx, int gx_bf16, const void *
                                        uint32_t *err_flag, void *stream) {
     if (!gx) return ASR_EINVAL;
     return lstm_fwd_impl(gx, gx_bf16, nullptr, nullptr, 0, whh_bf16, lens, T, B, H, y, y_bf16,
-                         gates_bf16, csave, nullptr, workspace, workspace_bytes, err_flag, stream);
+                         gates_bf16, csave, workspace, workspace_bytes, err_flag, stream);
 }
 
 extern "C" int asr_lstm_bidir_fwd_fused_bf16(const void *x_bf16, const void *wih_bf16,
@@ -1562,58 +1102,28 @@ extern "C" int asr_lstm_bidir_fwd_fused_bf16(const void *x_bf16, const void *wih
                                              void *stream) {
     if (!x_bf16 || !wih_bf16) return ASR_EINVAL;
     return lstm_fwd_impl(nullptr, 1, x_bf16, wih_bf16, F, whh_bf16, lens, T, B, H, y, y_bf16,
-                         gates_bf16, csave, nullptr, workspace, workspace_bytes, err_flag, stream);
+                         gates_bf16, csave, workspace, workspace_bytes, err_flag, stream);
 }
-
-#ifdef ASR_EXPERIMENTS   // include/asr_amd_experiments.h: not in the default library
-// ... and xsum [T,B,H] bf16 = bf16(h_fwd) + bf16(h_rev), the next layer's input (BatchRNN's
-// direction merge, encoder_utils.py:112-117, on the bf16 planes): the recurrence runs as TWO
-// launches, steps [0, ceil(T/2)) and the rest; in the second every frame a direction reaches
-// was written by the other one in the first, so it adds that value to its own output — no
-// separate pass over the planes (0.1 ms per layer at B=768), no cross-direction hand-shake.
-// For odd T the middle frame is reached by both directions in the first launch: it is left
-// to the caller (xsum[T/2] is not written).
-extern "C" int asr_lstm_bidir_fwd_fused_sum_bf16(const void *x_bf16, const void *wih_bf16,
-                                                 const void *whh_bf16, const int32_t *lens,
-                                                 int T, int B, int H, int F, float *y, void *y_bf16,
-                                                 void *gates_bf16, float *csave, void *xsum_bf16,
-                                                 void *workspace, int64_t workspace_bytes,
-                                                 uint32_t *err_flag, void *stream) {
-    if (!x_bf16 || !wih_bf16 || !xsum_bf16) return ASR_EINVAL;
-    if (T < 2) return ASR_EUNSUPPORTED;
-    return lstm_fwd_impl(nullptr, 1, x_bf16, wih_bf16, F, whh_bf16, lens, T, B, H, y, y_bf16,
-                         gates_bf16, csave, xsum_bf16, workspace, workspace_bytes, err_flag, stream);
-}
-#endif
 
 extern "C" int asr_lstm_fused_supported(int B, int H, int F) {
     if (!persist_enabled() || B <= 0) return 0;
     if (H != 64 && H != 128 && H != 256 && H != 320) return 0;
-    // input size: the hidden size, or (H = 320) the 352 features of the conv front-end —
-    // forward only
-    // bit 2: asr_lstm_bidir_fwd_fused_sum_bf16 (H = 320; not the 352-feature layer at 32-row tiles)
-    if (F != H)
-        return (H == 320 && F == 352 && cu_count() >= 2 * (H / 64))
-                   ? 1 | (pick_tile_rows(B, H / 64, cu_count()) < 4 ? 4 : 0) : 0;
-    const int cus = cu_count(), njt = H / 64;
-    if (cus < 2 * njt) return 0;
-    // bit 0: forward (input projection); bit 1: backward (input gradient) — its kernel has no
-    // LDS left for 32-row batch tiles, i.e. the batch must fit one launch of 16/24-row tiles
-    return 1 | (pick_tile_rows(B, njt, cus) < 4 ? 2 : 0) | (H == 320 ? 4 : 0);
+    // input size: the hidden size, or (H = 320) the 352 features of the conv front-end
+    if (F != H && !(H == 320 && F == 352)) return 0;
+    return cu_count() >= 2 * (H / 64) ? 1 : 0;
 }
 
 namespace {
 int lstm_fwd_impl(const void *gx, int gx_bf16, const void *x_bf16, const void *wih_bf16, int F,
                   const void *whh_bf16, const int32_t *lens, int T, int B, int H,
-                  float *y, void *y_bf16, void *gates_bf16, float *csave, void *xsum_bf16,
+                  float *y, void *y_bf16, void *gates_bf16, float *csave,
                   void *workspace, int64_t workspace_bytes, uint32_t *err_flag, void *stream) {
     const bool fused = x_bf16 != nullptr;
-    if (xsum_bf16 && !fused) return ASR_EINVAL;
     if (T < 0 || B <= 0 || H <= 0 || (H % 32) != 0) return ASR_EINVAL;
     if (T == 0) return ASR_OK;
     if (!whh_bf16 || !lens || !y_bf16 || !gates_bf16 || !csave || !workspace)
         return ASR_EINVAL;
-    if (fused && (!(asr_lstm_fused_supported(B, H, F) & 1) || (uint64_t)T * B * F * 2 >= (1ull << 31)))
+    if (fused && (!asr_lstm_fused_supported(B, H, F) || (uint64_t)T * B * F * 2 >= (1ull << 31)))
         return ASR_EUNSUPPORTED;
     if (fused && F != H && y) return ASR_EINVAL;      // that variant writes the bf16 outputs only
     if (workspace_bytes < asr_lstm_workspace_bytes(B, H)) return ASR_EINVAL;
@@ -1628,7 +1138,7 @@ int lstm_fwd_impl(const void *gx, int gx_bf16, const void *x_bf16, const void *w
     p.hbuf = (__bf16 *)workspace;
     p.cbuf = (float *)((char *)workspace + hbytes);
     p.y = y; p.ybf = (__bf16 *)y_bf16; p.gates = (u32x2 *)gates_bf16; p.csave = csave;
-    p.step = 0; p.s_begin = 0; p.s_end = T; p.xsum = nullptr;
+    p.step = 0;
     ZeroList zl;
     zl.add(workspace, hbytes + cbytes);
     // the two pad frames of every direction of y_bf16
@@ -1663,39 +1173,21 @@ int lstm_fwd_impl(const void *gx, int gx_bf16, const void *x_bf16, const void *w
             pk[0] = lstm_fwd_persist_kernel<20, 2, 1, 22>; pk[1] = lstm_fwd_persist_kernel<20, 3, 1, 22>;
             pk[2] = lstm_fwd_persist_kernel<20, 4, 1, 22>;
         }
-        // the second launch of the direction-sum variant (H = 320 only; the 32-row tile kernel
-        // of the 352-feature layer has no register left for it: that layer's caller adds)
-        void (*pks[3])(LstmFwdParams, LstmTeamCtl) = {nullptr, nullptr, nullptr};
-        if (H == 320 && fused && F == H) {
-            pks[0] = lstm_fwd_persist_kernel<20, 2, 1, 20, 1>; pks[1] = lstm_fwd_persist_kernel<20, 3, 1, 20, 1>;
-            pks[2] = lstm_fwd_persist_kernel<20, 4, 1, 20, 1>;
-        }
-        if (H == 320 && fused && F == 352) {
-            pks[0] = lstm_fwd_persist_kernel<20, 2, 1, 22, 1>; pks[1] = lstm_fwd_persist_kernel<20, 3, 1, 22, 1>;
-        }
-        if (xsum_bf16 && !pks[pick_tile_rows(B, H / 64, cu_count()) - 2]) return ASR_EUNSUPPORTED;
         // the persistent kernel addresses gx / y / gates / ... with 32-bit byte offsets
         const bool fits32 = (uint64_t)T * B * 8 * H * 4 < (1ull << 32) &&
                             (uint64_t)2 * (T + 2) * B * H * 2 < (1ull << 32);
-        const size_t lds_need = (size_t)(H / 16) * 1024 + (fused ? (size_t)(F / 16) * 1024 + 8192 : 0) + ASR_GLDS_BYTES + 4096;
-        if (xsum_bf16) p.s_end = (T + 1) / 2;
-        if (fits32 && pk[2] && launch_persist(pk, p, B, H, lds_need, ctl_words, err_flag, s)) {
-            if (xsum_bf16) {        // the second half: same counters, state from hbuf / csave
-                p.s_begin = p.s_end; p.s_end = T; p.xsum = (__bf16 *)xsum_bf16;
-                if (!launch_persist(pks, p, B, H, lds_need, ctl_words, err_flag, s)) return ASR_ELAUNCH;
-            }
+        const size_t lds_need = (size_t)(H / 16) * 1024 + (fused ? (size_t)(F / 16) * 1024 : 0) + ASR_GLDS_BYTES + 4096;
+        if (fits32 && pk[2] && launch_persist(pk, p, B, H, lds_need, ctl_words, err_flag, s))
             return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
-        }
     }
     if (fused) return ASR_EUNSUPPORTED;
-    // one launch per step.  64-row tiles (bt = 2) halve the W_hh re-reads but were
+    // one launch per step.  64-row tiles would halve the W_hh re-reads but were
     // measured SLOWER (13.7 vs 11.4 us at B=512): the step is latency-bound per
     // workgroup, not fetch-bound
-    const int bt = 1;
-    const dim3 grid(H / 32, (B + 32 * bt - 1) / (32 * bt), 2);
+    const dim3 grid(H / 32, (B + 31) / 32, 2);
     void (*kern)(LstmFwdParams) = nullptr;
 #define ASR_PICK(KSV)                                                              \
-    if (H == 16 * KSV) kern = gx_bf16 ? lstm_fwd_step_kernel<KSV, 1, 1> : lstm_fwd_step_kernel<KSV, 1, 0>;
+    if (H == 16 * KSV) kern = gx_bf16 ? lstm_fwd_step_kernel<KSV, 1> : lstm_fwd_step_kernel<KSV, 0>;
     ASR_PICK(20) ASR_PICK(4) ASR_PICK(8) ASR_PICK(16) ASR_PICK(24) ASR_PICK(32) ASR_PICK(48)
 #undef ASR_PICK
     if (!kern) return ASR_EUNSUPPORTED;       // hidden sizes built: 64,128,256,320,384,512,768
@@ -1707,47 +1199,16 @@ int lstm_fwd_impl(const void *gx, int gx_bf16, const void *x_bf16, const void *w
 }
 }  // namespace
 
-namespace {
-int lstm_bwd_impl(const float *dy, int dy_shared, const void *whhT_bf16, const void *wihT_bf16,
-                  const int32_t *lens, int T, int B, int H, const void *gates_bf16,
-                  const float *csave, void *dgates_bf16, float *dx, void *workspace,
-                  int64_t workspace_bytes, uint32_t *err_flag, void *stream);
-}
-
 extern "C" int asr_lstm_bidir_bwd_bf16(const float *dy, int dy_shared, const void *whhT_bf16,
                                        const int32_t *lens, int T, int B, int H,
                                        const void *gates_bf16, const float *csave,
                                        void *dgates_bf16,
                                        void *workspace, int64_t workspace_bytes,
                                        uint32_t *err_flag, void *stream) {
-    return lstm_bwd_impl(dy, dy_shared, whhT_bf16, nullptr, lens, T, B, H, gates_bf16, csave,
-                         dgates_bf16, nullptr, workspace, workspace_bytes, err_flag, stream);
-}
-
-#ifdef ASR_EXPERIMENTS   // include/asr_amd_experiments.h: not in the default library
-extern "C" int asr_lstm_bidir_bwd_fused_bf16(const float *dy, int dy_shared, const void *whhT_bf16,
-                                             const void *wihT_bf16, const int32_t *lens,
-                                             int T, int B, int H, const void *gates_bf16,
-                                             const float *csave, void *dgates_bf16, float *dx,
-                                             void *workspace, int64_t workspace_bytes,
-                                             uint32_t *err_flag, void *stream) {
-    if (!wihT_bf16 || !dx) return ASR_EINVAL;
-    return lstm_bwd_impl(dy, dy_shared, whhT_bf16, wihT_bf16, lens, T, B, H, gates_bf16, csave,
-                         dgates_bf16, dx, workspace, workspace_bytes, err_flag, stream);
-}
-#endif
-
-namespace {
-int lstm_bwd_impl(const float *dy, int dy_shared, const void *whhT_bf16, const void *wihT_bf16,
-                  const int32_t *lens, int T, int B, int H, const void *gates_bf16,
-                  const float *csave, void *dgates_bf16, float *dx, void *workspace,
-                  int64_t workspace_bytes, uint32_t *err_flag, void *stream) {
-    const bool fused = wihT_bf16 != nullptr;
-    if (T < 0 || B <= 0 || H <= 0 || (H % 32) != 0 || dy_shared < 0 || dy_shared > 2) return ASR_EINVAL;
+    if (T < 0 || B <= 0 || H <= 0 || (H % 32) != 0 || dy_shared < 0 || dy_shared > 1) return ASR_EINVAL;
     if (T == 0) return ASR_OK;
     if (!dy || !whhT_bf16 || !lens || !gates_bf16 || !csave || !dgates_bf16 || !workspace)
         return ASR_EINVAL;
-    if (fused && !(asr_lstm_fused_supported(B, H, H) & 2)) return ASR_EUNSUPPORTED;
     if (workspace_bytes < asr_lstm_workspace_bytes(B, H)) return ASR_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     LstmBwdParams p;
@@ -1755,7 +1216,6 @@ int lstm_bwd_impl(const float *dy, int dy_shared, const void *whhT_bf16, const v
     const size_t dbytes = (size_t)2 * 2 * Bp * 4 * H * 2, cbytes = (size_t)2 * B * H * 4;
     __bf16 *wpack = (__bf16 *)((char *)workspace + dbytes + cbytes);
     p.dy = dy; p.dy_shared = dy_shared; p.whhT = wpack; p.lens = lens;
-    p.wihT = wpack + (size_t)2 * H * 4 * H; p.dx = dx;
     p.T = T; p.B = B; p.H = H;
     p.gates = (const u32x2 *)gates_bf16; p.csave = csave;
     p.dgbuf = (__bf16 *)workspace;
@@ -1771,33 +1231,22 @@ int lstm_bwd_impl(const float *dy, int dy_shared, const void *whhT_bf16, const v
     // whhT_bf16 is [2][H][4H] row-major: rows = hidden unit j, cols = k over 4H
     hipLaunchKernelGGL(lstm_pack_kernel, dim3(1024), dim3(256), 0, s,
                        (const __bf16 *)whhT_bf16, wpack, 2, H, 4 * H, 0);
-    if (fused)          // wihT_bf16 is [2][H (input feature)][4H] row-major
-        hipLaunchKernelGGL(lstm_pack_kernel, dim3(1024), dim3(256), 0, s,
-                           (const __bf16 *)wihT_bf16, wpack + (size_t)2 * H * 4 * H, 2, H, 4 * H, 0);
     if (persist_enabled()) {
         unsigned *ctl_words = (unsigned *)((char *)workspace + asr_lstm_workspace_bytes(B, H) - ctl_bytes(B));
         void (*pk[3])(LstmBwdParams, LstmTeamCtl) = {nullptr, nullptr, nullptr};
-#define ASR_PICK(KSV) if (H == 16 * KSV && !fused) { pk[0] = lstm_bwd_persist_kernel<KSV, 2>; \
+#define ASR_PICK(KSV) if (H == 16 * KSV) { pk[0] = lstm_bwd_persist_kernel<KSV, 2>; \
         pk[1] = lstm_bwd_persist_kernel<KSV, 3>; pk[2] = lstm_bwd_persist_kernel<KSV, 4>; }
         ASR_PICK(20) ASR_PICK(4) ASR_PICK(8) ASR_PICK(16) ASR_PICK(24)
 #undef ASR_PICK
-#define ASR_PICK(KSV) if (H == 16 * KSV && fused) { pk[0] = lstm_bwd_dx_kernel<KSV, 2>; \
-        pk[1] = lstm_bwd_dx_kernel<KSV, 3>; }
-        ASR_PICK(20) ASR_PICK(4) ASR_PICK(8) ASR_PICK(16)
-#undef ASR_PICK
-        // 32-bit byte offsets (the fused kernel marks masked lanes with offset 2^31: half the range)
-        const bool fits32 = (uint64_t)T * B * 8 * H * 4 < (fused ? (1ull << 31) : (1ull << 32));
-        const size_t lds = (size_t)(H / 4) * 1024 + ASR_GLDS_BYTES + 16384 + (fused ? 24 * 1280 : 0);
-        if (fits32 && (pk[2] || fused) && launch_persist(pk, p, B, H, lds, ctl_words, err_flag, s))
+        const bool fits32 = (uint64_t)T * B * 8 * H * 4 < (1ull << 32);      // 32-bit byte offsets
+        const size_t lds = (size_t)(H / 4) * 1024 + ASR_GLDS_BYTES + 16384;
+        if (fits32 && pk[2] && launch_persist(pk, p, B, H, lds, ctl_words, err_flag, s))
             return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
     }
-    // the per-step kernels know neither the fused input gradient nor the two-plane dy
-    if (fused || dy_shared == 2) return ASR_EUNSUPPORTED;
-    const int bt = 1;
-    const dim3 grid(H / 32, (B + 32 * bt - 1) / (32 * bt), 2);
+    const dim3 grid(H / 32, (B + 31) / 32, 2);
     void (*kern)(LstmBwdParams) = nullptr;
 #define ASR_PICK(KSV)                                                              \
-    if (H == 16 * KSV) kern = bt == 2 ? lstm_bwd_step_kernel<KSV, 2> : lstm_bwd_step_kernel<KSV, 1>;
+    if (H == 16 * KSV) kern = lstm_bwd_step_kernel<KSV>;
     ASR_PICK(20) ASR_PICK(4) ASR_PICK(8) ASR_PICK(16) ASR_PICK(24) ASR_PICK(32) ASR_PICK(48)
 #undef ASR_PICK
     if (!kern) return ASR_EUNSUPPORTED;
@@ -1807,4 +1256,3 @@ int lstm_bwd_impl(const float *dy, int dy_shared, const void *whhT_bf16, const v
     }
     return hipGetLastError() == hipSuccess ? ASR_OK : ASR_ELAUNCH;
 }
-}  // namespace

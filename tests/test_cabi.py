@@ -26,17 +26,12 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_experiments_stay_out_of_the_default_library():
-    """include/asr_amd_experiments.h: variants that lost against the default path are exported
-    only by a `make EXPERIMENTS=1` build, all of them or none."""
+    """The two LSTM recurrence variants that lost against the default path
+    were removed: the library exports neither of their entry points."""
     from att_speech import _native
-    names = _declared('asr_amd_experiments.h')
-    assert set(names) == set(_native._EXPERIMENT_SIGNATURES)
-    assert not set(names) & set(_declared())
     handle = ctypes.CDLL(_native.LIB_PATH)
-    have = [hasattr(handle, n) for n in names]
-    assert all(have) == _native.experiments_built() and (all(have) or not any(have))
-    if os.environ.get('ASR_EXPECT_EXPERIMENTS', '0') != '1':
-        assert not any(have), 'the default build must not export experiment entry points'
+    for n in ('asr_lstm_bidir_bwd_fused_bf16', 'asr_lstm_bidir_fwd_fused_sum_bf16'):
+        assert not hasattr(handle, n), n
 
 
 def test_argument_checks_need_no_gpu():
@@ -52,6 +47,9 @@ def test_argument_checks_need_no_gpu():
     assert L.asr_log_softmax_fwd_f32(None, 4, 0, None, None) == _native.ASR_EINVAL
     assert L.asr_log_softmax_fwd_f32(None, 0, 7, None, None) == _native.ASR_OK
     assert L.asr_lattice_fwbw_workspace_bytes(10, 2, 5, 7) >= 10 * 2 * 7 * 4
+    # dy_shared is 0 or 1: the range check comes first (before T == 0 and the pointer checks)
+    assert L.asr_lstm_bidir_bwd_bf16(None, 2, None, None, 0, 1, 32, None, None, None, None, 0,
+                                     None, None) == _native.ASR_EINVAL
 
 
 def test_cpu_tensors_are_refused_loudly():

@@ -207,48 +207,6 @@ def test_fused_input_projection_first_layer_shape(T, B, reps):
     _fused_projection_case(T, B, 320, 352, reps)
 
 
-@pytest.mark.parametrize('T,B,F', [(2, 3, 320), (23, 7, 320), (24, 40, 320), (151, 96, 320), (334, 576, 320),
-                                   (334, 768, 320), (40, 900, 320), (23, 7, 352), (150, 96, 352), (334, 576, 352)])
-def test_direction_sum_inside_the_recurrence(T, B, F):
-    """asr_lstm_bidir_fwd_fused_sum_bf16: the recurrence as two launches (steps [0, ceil(T/2)) and
-    the rest, the second picking its state up from the hand-off buffer / csave), the second
-    adding the other direction's bf16 output of each frame to its own.  Every output must be
-    bit-identical to the single launch (same arithmetic; a wrong restored state, a stale tile
-    or a missed frame changes bits), xsum bit-identical to the add over the two planes; odd
-    and even T, ragged lengths, 16/24/32-row tiles, a batch that needs several launches."""
-    from att_speech import _native
-    dev = torch.device('cuda:0')
-    H = 320
-    if not _native.experiments_built():
-        pytest.skip('experiment: needs a `make EXPERIMENTS=1` library (include/asr_amd_experiments.h)')
-    if not _native.lstm_fused_supported(B, H, F=F, dirsum=True):
-        pytest.skip('no direction-sum kernel for this (batch, input size)')
-    g = torch.Generator().manual_seed(T * 13 + B + F)
-    lens = torch.randint(1, T + 1, (B,), generator=g).sort(descending=True)[0]
-    lens[0] = T
-    x = torch.randn(T, B, F, generator=g).to(dev, torch.bfloat16)
-    wih = (torch.randn(8 * H, F, generator=g) * (1.0 / F ** 0.5)).to(dev, torch.bfloat16)
-    whh = (torch.randn(2, 4 * H, H, generator=g) * (1.0 / H ** 0.5)).to(dev, torch.bfloat16)
-    lens_d = lens.to(dev, torch.int32)
-    want_y = F == H
-    one = _native.lstm_bidir_fwd_fused(x, wih, whh, lens_d, want_y=want_y)
-    act = (torch.arange(T)[:, None] < lens[None, :]).to(dev)
-    for _ in range(2):
-        two = _native.lstm_bidir_fwd_fused(x, wih, whh, lens_d, want_y=want_y, want_sum=True)
-        torch.cuda.synchronize()
-        _native.lstm_check_errors()
-        for name, a, b in zip(('y', 'y_bf16', 'gates', 'csave'), two, one):
-            if a is None:
-                continue
-            if name == 'gates':         # records of padding frames are never written
-                m = act[:, None, :, None, None].expand_as(a)
-                a, b = a[m], b[m]
-            assert torch.equal(a.view(torch.int16 if a.dtype == torch.bfloat16 else torch.int32),
-                               b.view(torch.int16 if b.dtype == torch.bfloat16 else torch.int32)), name
-        want = one[1][0, 1:T + 1] + one[1][1, 1:T + 1]
-        assert torch.equal(two[4].view(torch.int16), want.view(torch.int16))
-
-
 def _fused_projection_case(T, B, H, F, reps):
     """asr_lstm_bidir_fwd_fused_bf16 (x_t·W_ih inside the persistent kernel, the tile brought
     in by LDS-DMA under the hand-off waits) against the fp32 product of the same bf16
@@ -269,6 +227,8 @@ def _fused_projection_case(T, B, H, F, reps):
     whh = (torch.randn(2, 4 * H, H, generator=g) * (1.0 / H ** 0.5)).to(dev, torch.bfloat16)
     lens_d = lens.to(dev, torch.int32)
     assert _native.lstm_fused_supported(B, H, F=F)
+    for shape in ((24, 320, 320), (24, 320, 352), (900, 320, 320)):     # the raw word: no further bits
+        assert _native.lib().asr_lstm_fused_supported(*shape) in (0, 1), shape
     want_y = F == H
     gx = torch.mm(x.view(T * B, F), wih.t(), out_dtype=torch.float32).view(T, B, 2, 4 * H)
     ref = _native.lstm_bidir_fwd(gx, whh, lens_d)
@@ -304,55 +264,6 @@ def _fused_projection_case(T, B, H, F, reps):
     assert out[0] is None and torch.equal(out[1], first[1])
 
 
-@pytest.mark.parametrize('T,B,H,reps', [
-    (1, 1, 64, 1),
-    (2, 3, 64, 1),
-    (23, 7, 64, 1),
-    (61, 45, 128, 1),
-    (19, 70, 256, 1),
-    (150, 96, 320, 1),
-    (334, 512, 320, 3),        # bench shape, repeated
-])
-def test_fused_input_gradient_matches_recurrence_plus_gemm(T, B, H, reps):
-    """asr_lstm_bidir_bwd_fused_bf16 (dx = dgates·W_ih inside the persistent backward kernel,
-    hand-off tile and pointwise operands by LDS-DMA) against asr_lstm_bidir_bwd_bf16 + the
-    GEMM: the gate gradients go through the same arithmetic in the same order, so they must
-    agree bit for bit (a stale tile, a late operand or a torn hand-off changes bits); the
-    sum of the two dx planes is the fp32 product of the same bf16 operands up to summation
-    order.  Also: a gradient handed in as two planes equals the same gradient pre-summed."""
-    from att_speech import _native
-    dev = torch.device('cuda:0')
-    if not _native.experiments_built():
-        pytest.skip('experiment: needs a `make EXPERIMENTS=1` library (include/asr_amd_experiments.h)')
-    g = torch.Generator().manual_seed(T * 13 + B)
-    lens = torch.randint(1, T + 1, (B,), generator=g).sort(descending=True)[0]
-    lens[0] = T
-    gx = (torch.randn(T, B, 2, 4 * H, generator=g) * 1.5).to(dev)
-    whh = (torch.randn(2, 4 * H, H, generator=g) * (1.0 / H ** 0.5)).to(dev, torch.bfloat16)
-    wih = (torch.randn(2, 4 * H, H, generator=g) * (1.0 / H ** 0.5)).to(dev, torch.bfloat16)
-    dya = torch.randn(T, B, H, generator=g).to(dev)
-    dyb = torch.randn(T, B, H, generator=g).to(dev)
-    lens_d = lens.to(dev, torch.int32)
-    assert _native.lstm_fused_supported(B, H, backward=True)
-    _, _, gates, csave = _native.lstm_bidir_fwd(gx, whh, lens_d)
-    whhT, wihT = whh.transpose(1, 2).contiguous(), wih.transpose(1, 2).contiguous()
-    dy = dya + dyb
-    want = _native.lstm_bidir_bwd(dy, whhT, lens_d, gates, csave)
-    want_dx = torch.mm(want.view(T * B, 8 * H), wih.view(8 * H, H), out_dtype=torch.float32).view(T, B, H)
-    for _ in range(reps):
-        for planes in (False, True):
-            arg = torch.stack([dya, dyb]) if planes else dy
-            dg, dx = _native.lstm_bidir_bwd_fused(arg, whhT, wihT, lens_d, gates, csave, planes=planes)
-            torch.cuda.synchronize()
-            _native.lstm_check_errors()
-            assert torch.equal(dg, want), float((dg.float() - want.float()).abs().max())
-            got = dx[0] + dx[1]
-            assert float((got - want_dx).abs().max()) <= 2e-3 * (1.0 + float(want_dx.abs().max()))
-    # the unfused kernel takes planes too (the layer below a fused one)
-    dg = _native.lstm_bidir_bwd(torch.stack([dya, dyb]), whhT, lens_d, gates, csave, planes=True)
-    assert torch.equal(dg, want)
-
-
 def test_handoff_timeout_surfaces_as_an_error(monkeypatch):
     """A persistent-recurrence hand-off whose spin bound expires poisons the outputs with
     NaN and sets the caller's error word; `_native.lstm_check_errors` (called once per step
@@ -380,14 +291,11 @@ def test_handoff_timeout_surfaces_as_an_error(monkeypatch):
     assert bool(torch.isfinite(y).all())
 
 
-@pytest.mark.parametrize('fused_bwd', [False, True])
-def test_layer_stack_matches_chained_layers(fused_bwd, monkeypatch):
+def test_layer_stack_matches_chained_layers():
     """native_lstm.bilstm_stack (one autograd node, bf16 planes between layers, no fp32 outputs
     of the inner layers) against the same layers applied one by one with summed directions:
     outputs and all gradients agree at the level of the bf16 inter-layer operand."""
     from att_speech.modules.encoders.native_lstm import bilstm, bilstm_stack
-    if fused_bwd:       # the opt-in input-gradient fusion (dx planes handed from layer to layer)
-        monkeypatch.setenv('ASR_LSTM_FUSED_BWD', '1')
     torch.manual_seed(5)
     dev = torch.device('cuda:0')
     T, B, F, H = 23, 37, 96, 128

@@ -32,7 +32,6 @@ for _ in range(3):
         y, ybf, gates, cs = _native.lstm_bidir_fwd_fused(x, wih, whh, lens)
     else:
         y, ybf, gates, cs = _native.lstm_bidir_fwd(gx, whh, lens)
-    # (the backward the step runs: the fused-input-gradient variant is opt-in, ASR_LSTM_FUSED_BWD)
     dg = _native.lstm_bidir_bwd(dy, whhT, lens, gates, cs)
 torch.cuda.synchronize()
 R = int(os.environ.get('TILE_ROWS', '24'))    # batch rows per tile the host picked (24 at B=512)
